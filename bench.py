@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — RegisterIdentityBuilder witnesses/s on MI355X (BASELINE.json metric).
 
-python bench.py --gpus N --steps K --warmup W [--workload register|sha256]
+python bench.py --gpus N --steps K --warmup W [--workload register|sha256] [--dump-outputs DIR] [--full]
 
 One step = one pass of the hot path over one batch of synthetic passports per GPU
 (batch 4096 of the canonical instance RegisterIdentityBuilder(1,256,3,4,600,248,1,1496,3,256),
@@ -9,7 +9,10 @@ SURVEY.md §8d config 3), inputs already resident in HBM when the timed region s
 A full --O0 witness is ~72 MB, so a 4096 batch (~295 GB) does not fit one GPU's 288 GB:
 each step runs it as sub-batches into a reused output slab (every witness is fully
 written). N > 1 shards the batch (weak scaling, no data-path collective).
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps and reports them (value, ms_per_step,
+the rooflines from the phase timers of those steps); --dump-outputs DIR then writes what the last timed step computed.
+--full adds the legs that take runs of their own: the gathered status / public-signal pass, the embedded config 4,
+host_delivered, input_side and cpu_baseline.
 """
 import argparse
 import glob
@@ -296,6 +299,55 @@ class GpuEngine:
         torch.cuda.synchronize(self.dev)
         return st, pub
 
+    def outputs(self, k):
+        """What timed step k left with the caller, for --dump-outputs: the lane statuses of the whole batch, and a
+        sample (sample_plan) of the witness rows resident in the output slots after the step."""
+        view = self.d_out.view(self.slots * self.sub, self.W, 32)
+        pos, wit, cols = sample_plan(self.batch, self.sub, self.slots, self.W)
+        cols_d = self.torch.from_numpy(cols).to(self.dev)
+        rows = [view[int(p)].index_select(0, cols_d).cpu().numpy() for p in pos]
+        return {"status": self.d_st[k].cpu().numpy().astype(np.float64),
+                "witness_sample": limbs_f64(np.stack(rows))}
+
+
+DUMP_ROWS, DUMP_COLS, DUMP_SEED = 16, 16384, 0x64756d70
+
+
+def sample_plan(batch, sub, slots, W):
+    """The fixed sample --dump-outputs takes of a step's witnesses. A step writes sub-batch j into output slot
+    j % slots, so after it each slot holds its last sub-batch. -> (slab row, batch index, signal index arrays): up to
+    DUMP_ROWS resident witnesses and, of each, the first 64 elements (1, the public signals) and DUMP_COLS more, all
+    chosen by a generator seeded with DUMP_SEED (the same for equal batch / sub / slots / W)."""
+    pos, wit = [], []
+    nsub = (batch + sub - 1) // sub
+    for j in range(max(0, nsub - slots), nsub):
+        n = min(sub, batch - j * sub)
+        pos += [(j % slots) * sub + i for i in range(n)]
+        wit += [j * sub + i for i in range(n)]
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = np.sort(rng.choice(len(pos), size=min(DUMP_ROWS, len(pos)), replace=False))
+    head = min(64, W)
+    cols = np.arange(head)
+    if W > head:
+        rest = head + np.sort(rng.choice(W - head, size=min(DUMP_COLS, W - head), replace=False))
+        cols = np.concatenate([cols, rest]).astype(np.int64)
+    return np.asarray(pos)[pick], np.asarray(wit)[pick], cols
+
+
+def limbs_f64(elems):
+    """[..., 32] uint8 field elements (little endian) -> [..., 8] float64: their u32 limbs, each exact in a double"""
+    return np.ascontiguousarray(elems).view("<u4").astype(np.float64)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float64; 64 MB in all at the most)"""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20 and all(a.dtype == np.float64 for a in arrays.values()), total
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("outputs: %s (%.1f MB) written to %s" % (", ".join(sorted(arrays)), total / 1e6, path))
+
 
 def host_rows(args, workload, n, world):
     """Rank 0: the whole job's input rows of a workload on the host. -> (n, NIN, 32) uint8"""
@@ -420,16 +472,21 @@ def run_rank(args, rank, world, local, dist, engine_cls=GpuEngine, device="cuda"
 
     dt, bad = timed_steps(engine, args, dist)
     timing = engine.inst.timing() if hasattr(engine.inst, "timing") else None
-    st, pub = engine.public_pass()
+    if getattr(args, "dump_outputs", None) and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, engine.outputs(args.steps - 1))
     dt, bad = reduce_run(dist, dev, dt, bad)
-    if dist:
-        st, pub = D.gather_results(dist, st, pub, device=dev)
-    import hashlib
-    gathered = {"witnesses": int(st.shape[0]), "status_nonzero": int((st != 0).sum().item()),
-                "public_signals": int(pub.shape[1]),
-                "public_sha256": hashlib.sha256(pub.cpu().numpy().tobytes()).hexdigest()[:16]}
+    full = getattr(args, "full", False)  # the legs beside the headline figure (--full)
+    gathered = None
+    if full:
+        st, pub = engine.public_pass()
+        if dist:
+            st, pub = D.gather_results(dist, st, pub, device=dev)
+        import hashlib
+        gathered = {"witnesses": int(st.shape[0]), "status_nonzero": int((st != 0).sum().item()),
+                    "public_signals": int(pub.shape[1]),
+                    "public_sha256": hashlib.sha256(pub.cpu().numpy().tobytes()).hexdigest()[:16]}
     c4 = None
-    if wants_config4(args):
+    if full and wants_config4(args):
         t0 = time.time()
         full = None
         if rank == 0:
@@ -461,11 +518,17 @@ def main():
                     "committed circom-shaped maps), or synthetic[:N]")
     ap.add_argument("--smt-depth", default="0", help="register workloads: SMT proof depth of the synthetic "
                     "passports, N or A-B (uniform); default 0 (a one-leaf registration tree)")
-    ap.add_argument("--no-config4", action="store_true", help="default register line: skip the embedded config-4 "
-                    "measurement")
+    ap.add_argument("--full", action="store_true", help="after the headline figure also run the legs reported beside "
+                    "it: the gathered status / public-signal pass, the embedded config-4 measurement, host_delivered, "
+                    "input_side and cpu_baseline (each can be left out again with its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed as "
+                    "DIR/<name>.npy (float64): status (every lane) and witness_sample (u32 limbs of a fixed, seeded "
+                    "sample of the witness rows, sample_plan); with --gpus N, rank 0's shard")
+    ap.add_argument("--no-config4", action="store_true", help="--full, default register line: skip the embedded "
+                    "config-4 measurement")
     ap.add_argument("--cpu-sample", type=int, default=None)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-host", action="store_true", help="skip the host_delivered (streamed) measurement")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip cpu_baseline and input_side")
+    ap.add_argument("--no-host", action="store_true", help="--full: skip the host_delivered (streamed) measurement")
     ap.add_argument("--host-sample", type=int, default=None, help="witnesses streamed for host_delivered")
     args = ap.parse_args()
     if args.workload == "mixed" and os.environ.get("PZK_MIX_HWQ", "keep") != "keep":
@@ -670,11 +733,13 @@ def report(args, r, world):
             "job_hbm": {"achieved": round(g4, 1), "unit": "GB/s", "frac": round(g4 / (HBM_PEAK_GBS * world), 4)},
             "valu": valu_roofline(pm4[1], pm4[0], v4, world) if pm4 else None,
             "phases": phase_table(c4["timing"], info) if c4.get("timing") else None}
-    if world == 1 and not args.no_host and register_like(args.workload):
+    full = getattr(args, "full", False)
+    if full and world == 1 and not args.no_host and register_like(args.workload):
         out["host_delivered"] = host_delivered(args, r["engine"].inst, sig)
-    if world == 1 and not args.no_cpu and register_like(args.workload) and sig in (1, 3, 10, 11, 12, 20, 21, 24, 25):
+    if (full and world == 1 and not args.no_cpu and register_like(args.workload)
+            and sig in (1, 3, 10, 11, 12, 20, 21, 24, 25)):
         out["input_side"] = input_side(sig)
-    if world == 1 and not args.no_cpu:  # CPU baseline: N = 1 only (bounded sample)
+    if full and world == 1 and not args.no_cpu:  # CPU baseline: N = 1 only (bounded sample)
         procs = max(1, min(CPU_SHARE, os.cpu_count() or 1))
         if register_like(args.workload):
             ns = args.cpu_sample or (48 if sig >= 20 else 96 if sig == 11 else 128) * procs
@@ -920,6 +985,19 @@ class MixedGpuEngine:
     def statuses(self):
         return self.d_st
 
+    def outputs(self):
+        """What the last step left with the caller, for --dump-outputs: the shard's lane statuses and, per flow, a
+        sample (sample_plan) of the witness rows resident in its output slot."""
+        out = {"status": self.d_st.cpu().numpy().astype(np.float64)}
+        for sg, idx in self.groups.items():
+            W = self.witness_size[sg]
+            pos, _, cols = sample_plan(len(idx), self.sub[sg], 1, W)
+            view = self.d_out[sg].view(self.sub[sg], W, 32)
+            cols_d = self.torch.from_numpy(cols).to(self.dev)
+            rows = [view[int(p)].index_select(0, cols_d).cpu().numpy() for p in pos]
+            out["witness_sample_sig%d" % sg] = limbs_f64(np.stack(rows))
+        return out
+
     def public_pass(self, n_pub):
         """Untimed: status + public signals (witness[1 .. n_pub]) of every witness of the shard."""
         torch = self.torch
@@ -997,8 +1075,9 @@ def run_mixed_rank(args, rank, world, local, dist, engine_cls=MixedGpuEngine, de
         dist.barrier()
     dt = time.perf_counter() - t0
     bad = int((engine.statuses() != 0).sum().item())  # lanes failing in the last timed step
+    if getattr(args, "dump_outputs", None) and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, engine.outputs())
     n_pub = 5
-    st, pub = engine.public_pass(n_pub)
     my_bytes = sum(costs[lo:hi])
     if dist:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -1007,11 +1086,15 @@ def run_mixed_rank(args, rank, world, local, dist, engine_cls=MixedGpuEngine, de
         bt = torch.tensor([bad], device=dev, dtype=torch.int64)
         dist.all_reduce(bt)
         bad = int(bt.item())
-        st, pub = D.gather_results(dist, st, pub, device=dev)
-    import hashlib
-    gathered = {"witnesses": int(st.shape[0]), "status_nonzero": int((st != 0).sum().item()),
-                "public_sha256": hashlib.sha256(pub.cpu().numpy().tobytes()).hexdigest()[:16],
-                "order": "rank-major; within a rank grouped per flow (SIG 1, 2, 20), global order inside a group"}
+    gathered = None
+    if getattr(args, "full", False):  # the gathered status / public-signal pass is a run of its own (--full)
+        st, pub = engine.public_pass(n_pub)
+        if dist:
+            st, pub = D.gather_results(dist, st, pub, device=dev)
+        import hashlib
+        gathered = {"witnesses": int(st.shape[0]), "status_nonzero": int((st != 0).sum().item()),
+                    "public_sha256": hashlib.sha256(pub.cpu().numpy().tobytes()).hexdigest()[:16],
+                    "order": "rank-major; within a rank grouped per flow (SIG 1, 2, 20), global order inside a group"}
     value = total * args.steps / dt
     job_gbs = sum(costs) * args.steps / dt / 1e9
     return {

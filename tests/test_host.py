@@ -196,7 +196,7 @@ def _bench_rank(rank, world, port, q, workload="sha256"):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     args = argparse.Namespace(workload=workload, batch=6, sub=None, slots=1, steps=2, warmup=1,
                               sig_eff=1 if workload == "register" else 0, no_cpu=True,
-                              no_host=True,
+                              no_host=True, full=True,
                               gpus=world)
     r = bench.run_rank(args, rank, world, 0, dist, engine_cls=_StubEngine, device="cpu")
     if rank == 0:
@@ -350,7 +350,7 @@ def _mixed_rank(rank, world, port, q):
     import bench
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    args = argparse.Namespace(workload="mixed", batch=10, steps=2, warmup=1, gpus=world)
+    args = argparse.Namespace(workload="mixed", batch=10, steps=2, warmup=1, gpus=world, full=True)
     out = bench.run_mixed_rank(args, rank, world, 0, dist, engine_cls=_MixedStubEngine, device="cpu",
                                rows_fn=_mixed_stub_rows)
     if rank == 0:
@@ -424,3 +424,30 @@ def test_mixed_engine_call_order(monkeypatch):
         for sg, idx in e.groups.items():
             covered = sorted(r for g, a in calls if g == sg for r in range(a, min(a + e.sub[sg], len(idx))))
             assert covered == idx
+
+
+def test_dump_outputs_sample_plan(tmp_path):
+    """bench.py --dump-outputs: the sample of a step's witnesses is fixed by (batch, sub, slots, W), names only rows
+    resident after the step (sub-batch j lies in slot j % slots, a ragged last one included) and keeps the public
+    head of every sampled row; elements become their exact u32 limbs in float64; the files load back."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    pos, wit, cols = bench.sample_plan(10, 4, 1, 100)  # one slot: only the last sub-batch (witnesses 8, 9) is left
+    assert sorted(pos) == [0, 1] and sorted(wit) == [8, 9]
+    assert (cols[:64] == np.arange(64)).all() and (np.diff(cols) > 0).all() and cols[-1] < 100 and len(cols) == 100
+    pos, wit, cols = bench.sample_plan(10, 4, 2, 100)  # two slots: sub-batch 1 in slot 1, sub-batch 2 in slot 0
+    assert sorted(zip(pos, wit)) == [(0, 8), (1, 9), (4, 4), (5, 5), (6, 6), (7, 7)]
+    big = bench.sample_plan(4096, 2048, 1, 2251704)
+    again = bench.sample_plan(4096, 2048, 1, 2251704)
+    assert all((a == b).all() for a, b in zip(big, again))
+    assert len(big[0]) == bench.DUMP_ROWS and len(set(big[0])) == bench.DUMP_ROWS and big[0].max() < 2048
+    assert (big[1] == big[0] + 2048).all()
+    assert len(big[2]) == 64 + bench.DUMP_COLS and (np.diff(big[2]) > 0).all() and big[2][-1] < 2251704
+    vals = [0, 1, P - 1, 0x0123456789ABCDEF << 96]
+    elems = np.stack([np.frombuffer(v.to_bytes(32, "little"), dtype=np.uint8) for v in vals])
+    limbs = bench.limbs_f64(elems)
+    assert limbs.dtype == np.float64 and limbs.shape == (4, 8)
+    assert [sum(int(x) << (32 * i) for i, x in enumerate(row)) for row in limbs] == vals
+    bench.dump_outputs(str(tmp_path / "d"), {"status": np.zeros(3), "witness_sample": limbs})
+    assert (np.load(tmp_path / "d" / "witness_sample.npy") == limbs).all()
+    assert np.load(tmp_path / "d" / "status.npy").dtype == np.float64

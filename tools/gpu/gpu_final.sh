@@ -14,7 +14,7 @@ tail -1 $O/pytest.log
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
 echo "elapsed $(( $(date +%s) - T0 ))s"
-timeout -k 10 500 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+timeout -k 10 500 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
 python3 - "$O/bench_default.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
@@ -32,12 +32,12 @@ python3 -c "import json; d=json.load(open('$O/prof_bench.json')); print('profile
 cp "$f" $O/run_kernel_stats.csv
 rm -rf $O/prof
 echo "elapsed $(( $(date +%s) - T0 ))s"
-tools/gpu/gpu_lines.sh $TAG "query:--workload query --steps 20 --warmup 5" \
+tools/gpu/gpu_lines.sh $TAG "query:--workload query --steps 20 --warmup 5 --full" \
   "querytd1:--workload query-td1 --steps 20 --warmup 5 --no-cpu" \
-  "o2:--sym o2shape --steps 20 --warmup 5 --no-host --no-cpu" \
-  "o1:--sym o1shape --steps 20 --warmup 5 --no-host --no-cpu" \
-  "sha256:--workload sha256 --steps 20 --warmup 5" \
-  "poseidon:--workload poseidon --steps 20 --warmup 5" \
+  "o2:--sym o2shape --steps 20 --warmup 5 --full --no-host --no-cpu" \
+  "o1:--sym o1shape --steps 20 --warmup 5 --full --no-host --no-cpu" \
+  "sha256:--workload sha256 --steps 20 --warmup 5 --full" \
+  "poseidon:--workload poseidon --steps 20 --warmup 5 --full" \
   "sig20:--sig 20 --steps 10 --warmup 2 --no-host --no-cpu" \
-  "mixed:--workload mixed --steps 6 --warmup 2" &&
+  "mixed:--workload mixed --steps 6 --warmup 2 --full" &&
 echo "elapsed $(( $(date +%s) - T0 ))s" && echo EXIT 0
