@@ -112,8 +112,11 @@ enum {
   PZK_ST_CIT_BLACKLIST = 21, /* citizenshipCheck.circom:271 (the citizenship is in the mask) */
   PZK_ST_CIT_LIST = 22,   /* citizenshipCheck.circom:274 (the citizenship is not in COUNTRY_ARR) */
   PZK_ST_ISV_ROOT = 23,   /* identityStateVerifier.circom:46 (smtVerifier.isVerified === 1) */
-  PZK_ST_INPUT_RANGE = 64 /* an input outside the domain the GPU path evaluates (e.g. a non-bit
-                             SHA input, a limb >= 2^64); see DESIGN.md §5 */
+  PZK_ST_INPUT_RANGE = 64 /* an input outside the domain the GPU path evaluates: a non-bit SHA input, a
+                             limb >= 2^64, a field scalar >= p (skIdentity, the SMT root and siblings,
+                             eventID, eventData, pkPassportHash: raw bytes are not reduced). Other
+                             lanes of the batch are not affected; a lane that also fails a circuit
+                             check reports that smaller code. See DESIGN.md §5 */
 };
 
 enum {

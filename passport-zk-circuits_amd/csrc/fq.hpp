@@ -310,6 +310,19 @@ __device__ __forceinline__ fq fq_canon(const fq& a, const QLane& c) {
   return lt ? a : fq{e0, e1};
 }
 
+// a >= p for any 256-bit a (an input element as the caller wrote it): fq_canon's borrow, on every lane of the quad
+__device__ __forceinline__ bool fq_geq_p(const fq& a, const QLane& c) {
+  uint64_t d = (uint64_t)a.lo - c.p0;
+  const uint32_t d0 = (uint32_t)d;
+  const uint32_t b1 = (uint32_t)(d >> 32) & 1u;
+  d = (uint64_t)a.hi - c.p1 - b1;
+  const uint32_t d1 = (uint32_t)d;
+  const bool g = ((d >> 32) & 1u) != 0, pr = (d0 | d1) == 0;
+  const uint32_t bin = quad_carry_in(g, pr);
+  const uint32_t bout = (g || (pr && bin)) ? 1u : 0u;
+  return qbcast<3>(bout) == 0;  // no borrow out of the top digit
+}
+
 // a + b (no reduction; callers keep the sum < 2^256)
 __device__ __forceinline__ fq fq_add_raw(const fq& a, const fq& b) {
   uint64_t s = (uint64_t)a.lo + b.lo;

@@ -240,6 +240,20 @@ __device__ __forceinline__ fr fr_sqr(const fr& a) {
 __device__ __forceinline__ fr fr_to_mont(const fr& a) { return fr_mul(a, fr_const(R2_)); }
 __device__ __forceinline__ fr fr_from_mont(const fr& a) { fr one = fr_zero(); one.v[0] = 1; return fr_mul(a, one); }
 
+// ---- input elements as the caller wrote them: any 256-bit value
+// a >= p
+__device__ __forceinline__ bool fr_geq_p(const fr& a) {
+  uint64_t br = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) { uint64_t d = (uint64_t)a.v[i] - P_[i] - br; br = (d >> 32) & 1; }
+  return br == 0;
+}
+// Montgomery form of a mod p, canonical, for ANY 256-bit a. fr_to_mont(a) = fr_mul(a, R^2) scans its first operand
+// whole in every iteration, so its accumulator stays below a + p + a bit: fine for a < 2p, but past 2^256 (its
+// "no final carry" word overflows) for a near 2^256. With the operands swapped the accumulator stays below
+// R^2 + p < 2p whatever a is, and the result is below (R^2 a + 2^256 p) / 2^256 < 2p before the final subtraction.
+__device__ __forceinline__ fr fr_to_mont_in(const fr& a) { return fr_mul(fr_const(R2_), a); }
+
 // a^(p-2) in Montgomery form; inverse of 0 is 0 (IsZero semantics, comparators.circom:17).
 // FAST = the FIPS product (throughput form, for kernels with many independent lanes per SIMD)
 template <bool FAST = false>

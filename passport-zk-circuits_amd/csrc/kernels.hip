@@ -19,15 +19,18 @@
 namespace pzk {
 
 // ------------------------------------------------------------------- value loads
-// value-store slot <- input element (normal form -> Montgomery)
+// value-store slot <- input element (normal form -> Montgomery). The first read of the inputs the layout takes as
+// field scalars (skIdentity, eventID, pkPassportHash, ...): an element >= p flags the lane and goes on
+// as its residue, canonical, as the circuit would read it.
 __global__ void k_load_values(const ValueLoad* loads, int n_loads, const uint8_t* inputs, uint64_t n_inputs,
-                              fr* values, uint32_t batch) {
+                              fr* values, int32_t* status, uint32_t batch) {
   uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
   int l = blockIdx.y;
   if (w >= batch || l >= n_loads) return;
   ValueLoad ld = loads[l];
   fr x = load_fr(inputs + 32ull * ((uint64_t)w * n_inputs + ld.in_off));
-  values[(size_t)ld.slot * batch + w] = fr_to_mont(x);
+  if (fr_geq_p(x)) lane_status(status ? status + w : nullptr, ST_INPUT_RANGE);
+  values[(size_t)ld.slot * batch + w] = fr_to_mont_in(x);
 }
 
 // ------------------------------------------------------------------- SHA core
@@ -311,10 +314,10 @@ hipError_t launch_wtns_gather(const uint8_t* o0, size_t o0_stride, const uint32_
 }
 
 hipError_t launch_load_values(const ValueLoad* loads, int n, const uint8_t* inputs, uint64_t n_inputs, fr* values,
-                              uint32_t batch, hipStream_t st) {
+                              int32_t* status, uint32_t batch, hipStream_t st) {
   if (n == 0) return hipSuccess;
   dim3 g((batch + 63) / 64, n);
-  hipLaunchKernelGGL(k_load_values, g, dim3(64), 0, st, loads, n, inputs, n_inputs, values, batch);
+  hipLaunchKernelGGL(k_load_values, g, dim3(64), 0, st, loads, n, inputs, n_inputs, values, status, batch);
   return hipGetLastError();
 }
 

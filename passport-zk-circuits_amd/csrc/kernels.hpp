@@ -20,7 +20,7 @@ struct ValueStore;
 struct Bufs;
 
 hipError_t launch_load_values(const ValueLoad* loads, int n, const uint8_t* inputs, uint64_t n_inputs, fr* values,
-                              uint32_t batch, hipStream_t st);
+                              int32_t* status, uint32_t batch, hipStream_t st);
 // SHA jobs [first, first + count); a job with src = 1 reads its message from the derived row
 hipError_t launch_sha_core(const DevLayout& L, const uint8_t* inputs, const uint8_t* derived, uint32_t first,
                            uint32_t count, uint32_t* sha_core, int32_t* status, uint32_t batch, hipStream_t st);

@@ -383,6 +383,10 @@ __global__ void __launch_bounds__(64 * QP_WAVES) k_qry_prep(DevLayout L, const u
   // inputs read as 64-bit integers: bounds, dates, timestamp, counter (the evaluated domain)
   const int u64_in[11] = {QI_CUR, QI_TSLO, QI_TSHI, QI_ICLO, QI_ICHI, QI_BDLO, QI_BDHI, QI_EDLO, QI_EDHI, Q.ts, Q.ic};
   for (int k = 0; k < 11; k++) bad |= !in_is_u64(Q.row + 32ull * u64_in[k]);
+  // eventData: a field scalar that no core kernel reads (the emitters square and copy it), so it is compared with p
+  // here; the others are where they are first read: k_load_values (eventID, skIdentity, pkPassportHash), k_smt_prep
+  // (idStateSiblings), the SMT chain (idStateRoot)
+  bad |= fr_geq_p(load_fr(Q.row + 32ull * QI_EVDATA));
   if (bad) set_status(st, ST_INPUT_RANGE);
   const uint64_t exp = f64[1], birth = f64[0], cur = Q.in(QI_CUR);
   // DateDecoder: dateEncoder.encoded === dateEncoded (dateDecoder.circom:22) for every decoded date

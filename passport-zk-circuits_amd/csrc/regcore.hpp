@@ -883,14 +883,20 @@ __global__ void __launch_bounds__(64 * SMT_PREP_WAVES) k_smt_prep(DevLayout L, c
   uint32_t zmask = 0;  // bit k: sibling i0 + k is zero
   // (the forward pass runs twice, before and after the workgroup's inversion: arrays kept across its barriers and its
   // register-hungry inversion went to scratch)
+  // The siblings are field scalars read here first: one >= p flags the witness. Zero is decided on the
+  // residue, the value the product takes (as bytes p and 2p are not zero, but their Montgomery form is: taken as
+  // non-zero they made the witness total 0, with it the workgroup's t_all and so every neighbour's inverses, round 6).
+  // The residues are canonical, so a product of non-zero ones is non-zero.
+  bool bad = false;
   auto forward = [&](bool park) {  // park: the exclusive prefixes go to the inverse slots (read back below)
     fr a = fr_mont_one();
 #pragma unroll
     for (int k = 0; k < NL; k++) {
       const fr sn = load_fr(row + 32ull * (R.in_br + i0 + k));
-      const bool z = fr_is_zero(sn);
+      if (!park) bad |= fr_geq_p(sn);
+      sm[k] = fr_to_mont_in(sn);
+      const bool z = fr_is_zero(sm[k]);
       zmask |= (uint32_t)z << k;
-      sm[k] = fr_to_mont(sn);
       if (park) core[i0 + k] = a;
       if (!z) a = fr_mul_fast(a, sm[k]);
     }
@@ -900,7 +906,15 @@ __global__ void __launch_bounds__(64 * SMT_PREP_WAVES) k_smt_prep(DevLayout L, c
   fr others, total;
   fr_group_others<G>(acc, others, total);
   const int g = (int)(threadIdx.x / G);
-  if (seg == 0) s_tot[g] = total;
+  // a flagged witness (any lane of its group) takes no part in the workgroup's shared total: 1 in its place
+  const bool wbad = live && ((__ballot(bad) >> ((threadIdx.x & 63u) & ~(uint32_t)(G - 1))) & ((1ull << G) - 1)) != 0;
+  if (seg == 0) {
+    fr t;  // (per-limb selects, as in fr_reduce_once)
+#pragma unroll
+    for (int k = 0; k < 8; k++) t.v[k] = wbad ? R1_[k] : total.v[k];
+    s_tot[g] = t;
+    if (wbad) set_status(status ? status + w : nullptr, ST_INPUT_RANGE);
+  }
   __syncthreads();
   if (threadIdx.x < 64) {
     const fr t = threadIdx.x < NW ? s_tot[threadIdx.x] : fr_mont_one();
@@ -1015,7 +1029,7 @@ __global__ void __launch_bounds__(64) k_smt_chain(DevLayout L, PosConsts K, cons
   fr child = leaf;  // root_j = leaf
   fr* pcore = pos_core + (size_t)w * L.pos_core_elems;
   const uint8_t* sib_row = row + 32ull * R.in_br;
-  fr sib = top > 0 ? fr_to_mont(load_fr(sib_row + 32ull * (top - 1))) : fr_zero();
+  fr sib = top > 0 ? fr_to_mont_in(load_fr(sib_row + 32ull * (top - 1))) : fr_zero();
   for (int i = top - 1; i >= 0; i--) {
     const fr sib_next_raw = i > 0 ? load_fr(sib_row + 32ull * (i - 1)) : fr_zero();  // before this level's stores
     const bool lr = lrs[gi][i] != 0;
@@ -1026,7 +1040,7 @@ __global__ void __launch_bounds__(64) k_smt_chain(DevLayout L, PosConsts K, cons
     }
     child = pos_perm_group<3, G, KL, PM>(Kl, jl == 1 ? lv : jl == 2 ? rv : fr_zero(), pcore + lv_core[i], jl);
     if (jl == 0) vs.at(R.v_smt_h + i, w) = child;  // root_i = H_i (st_top = 1 below j)
-    sib = fr_to_mont(sib_next_raw);
+    sib = fr_to_mont_in(sib_next_raw);
   }
   if (jl != 0) return;  // lane 0 wrote every level hash this kernel made
   // roots of every level: root_i = st_top_i * H_i + st_inew_i * leaf (SMTVerifier.circom:104-106)
@@ -1039,7 +1053,10 @@ __global__ void __launch_bounds__(64) k_smt_chain(DevLayout L, PosConsts K, cons
     roots[i] = r;
   }
   // isEqual(root_0, root): inverse of root - root_0
-  fr rin = fr_to_mont(load_fr(row + 32ull * R.in_root));
+  // the root input is a field scalar read here first: >= p flags the lane
+  const fr rin_raw = load_fr(row + 32ull * R.in_root);
+  if (fr_geq_p(rin_raw)) set_status(status ? status + w : nullptr, ST_INPUT_RANGE);
+  fr rin = fr_to_mont_in(rin_raw);
   fr dlt = fr_sub(rin, roots[0]);
   core[3 * SMT_LEVELS + 1] = fr_inv_sw(dlt);
   // smtVerifier.isVerified === 1 where the circuit asserts it (identityStateVerifier.circom:46; the register

@@ -971,7 +971,7 @@ static int batch_locked(pzk_instance* I, const uint8_t* d_inputs, size_t batch, 
               s_own = serial ? st : I->s_tail;
   if (d_status) HIPCHK(hipMemsetAsync(d_status, 0, sizeof(int32_t) * batch, st));
   { PhaseScope ps(T, slot, PH_LOAD, st);
-    HIPCHK(launch_load_values(I->d_loads, (int)lay.loads.size(), d_inputs, lay.n_inputs, S.d_values, B, st)); }
+    HIPCHK(launch_load_values(I->d_loads, (int)lay.loads.size(), d_inputs, lay.n_inputs, S.d_values, d_status, B, st)); }
   if (lay.is_query) {
     // QueryIdentity(80) (query.hpp): one chain on the call's chain stream — prep, the BabyJubJub key, Poseidon levels
     // 0-3 (sk hashes, nullifier, dg1 commitment, pk / position / value hashes), the SMT prep (needs the tree

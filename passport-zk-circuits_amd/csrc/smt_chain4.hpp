@@ -259,7 +259,11 @@ __global__ void __launch_bounds__(256) k_smt_chain4(DevLayout L, PosConsts K, co
     if (f & 4) root0 = vs.at(R.v_smt_h, w);
     if (f & 8) root0 = fr_add(root0, leaf_f);
   }
-  const fr rin = fq_gather(to_mont(fq_load(row + 32ull * R.in_root, c.q)));
+  // the root input is a field scalar read here first: >= p flags the lane; to_mont takes any 256-bit
+  // value to its canonical residue (fq_mulq scans `raw` a word at a time: its accumulator stays below R^2 + p)
+  const fq rin_raw = fq_load(row + 32ull * R.in_root, c.q);
+  if (fq_geq_p(rin_raw, c) && lq == 0) set_status(status ? status + w : nullptr, ST_INPUT_RANGE);
+  const fr rin = fq_gather(to_mont(rin_raw));
   const fr dlt = fr_sub(rin, root0);
   const fq inv = fq_canon2(fq_inv(fq_digit(dlt, c.q), c), c);
   if (quad == 0) fq_store(core + 3 * SMT_LEVELS + 1, inv, c.q);

@@ -7,7 +7,9 @@ against the CPU oracle rather than against another run of the same code:
 * an O2-shaped mapped instance (a monotone .sym keeping a quarter of the signals: odd calls' SHA emission on the
   second SHA stream) with back-to-back unsynchronised calls;
 * QueryIdentity(80) with more calls in flight than it has scratch sets' worth of chain streams (six sets over four
-  chain streams): eight unsynchronised calls.
+  chain streams): eight unsynchronised calls;
+* the same with 13 rows per call (query: eight calls; register: two), so the workgroups of the kernels that share one
+  inversion among their witnesses (k_qry_prep, k_rsa_inv, k_bjj_core) are partly live while other calls are in flight.
 
 Rows of every call are compared element for element with the oracle (sampled rows of each call)."""
 import numpy as np
@@ -100,5 +102,40 @@ def test_query_eight_calls_in_flight(oracle):
             assert rc == 0
             bad = np.nonzero((ref != out[r]).any(axis=1))[0]
             assert bad.size == 0, "call at %d row %d: %d elements differ" % (lo, r, bad.size)
+    del d_in
+    torch.cuda.empty_cache()
+
+
+# 13 = 8 + 5 rows per call: the second workgroup of k_qry_prep (QP_WAVES = 8, query.hpp) and of k_rsa_inv (RI_WAVES = 8,
+# regcore.hpp) holds 5 live witnesses and 3 dead waves, and k_bjj_core's only workgroup 13 of 16, while other calls are
+# in flight. Compared: the last row of the full workgroup, the first and the last row of the partly live one.
+ODD = 13
+
+
+def test_query_odd_batches_in_flight(oracle):
+    import torch
+    inst = native.Instance(native.PZK_CIRCUIT_QUERY, 80)
+    rng = SplitMix64(0x6D)
+    rows = np.stack([Q.pack(Q.make_query(rng, depth=[0, 1, 40, 79, None][i % 5])[0]) for i in range(8 * ODD)])
+    res, d_in = _calls(torch, [inst], rows, 8, ODD)
+    for _, lo, out, st in res:
+        assert (st == 0).all()
+        for r in (0, 7, 8, 12):
+            rc, ref = oracle.query_witness(rows[lo + r])
+            assert rc == 0
+            bad = np.nonzero((ref != out[r]).any(axis=1))[0]
+            assert bad.size == 0, "call at %d row %d: %d elements differ" % (lo, r, bad.size)
+    del d_in
+    torch.cuda.empty_cache()
+
+
+def test_register_odd_batches_in_flight(oracle):
+    import torch
+    inst = native.Instance(native.PZK_CIRCUIT_REGISTER, 0, I.CANONICAL)
+    rows = _register_rows(0x6E, 2 * ODD, lambda i: (7 * i) % 80)
+    res, d_in = _calls(torch, [inst], rows, 2, ODD)
+    for _, lo, out, st in res:
+        assert (st == 0).all()
+        _check_rows(oracle, rows[lo:lo + ODD], out, st, [7, 8, 12])
     del d_in
     torch.cuda.empty_cache()
