@@ -33,9 +33,14 @@ enum {
   PZK_CIRCUIT_SHA1 = 3,     /* Sha1HashChunks(blocks)        hasher/sha1/sha1.circom:7 */
   PZK_CIRCUIT_SHA384 = 4,   /* Sha384HashChunks(blocks)      hasher/sha2/sha384/sha384HashChunks.circom:8 */
   PZK_CIRCUIT_SHA512 = 5,   /* Sha512HashChunks(blocks)      hasher/sha2/sha512/sha512HashChunks.circom */
-  PZK_CIRCUIT_QUERY = 6     /* QueryIdentity(idTreeDepth = size_arg, 80)  identityManagement/queryIdentity.circom:37;
+  PZK_CIRCUIT_QUERY = 6,    /* QueryIdentity(idTreeDepth = size_arg, 80)  identityManagement/queryIdentity.circom:37;
                                BabyPbk (undefined in the snapshot) is the reference's BabyjubjubBase8Multiplication,
                                DESIGN.md §11 */
+  PZK_CIRCUIT_LIGHT = 7     /* RegisterIdentityLight(dg_hash_type, document_type)
+                               identityManagement/registerIdentityLight.circom:15; dg_hash_type 160, 224, 256, 384 or
+                               512, document_type 1 or 3, every other pzk_params field ignored; inputs dg1[1024],
+                               skIdentity; outputs dg1Commitment, dg1Hash, pkIdentityHash; no public inputs (the
+                               reference declares no main). BabyPbk as for QUERY, DESIGN.md §13 */
 };
 
 /* Template parameters of RegisterIdentityBuilder (registerIdentityBuilder.circom:41-52),
@@ -52,7 +57,7 @@ typedef struct pzk_params {
                                  SHA-224 signed attributes, SHA-256 encapsulated content), 25 = ECDSA
                                  brainpoolP384r1 (6 x 64-bit chunks, SHA-384). 22 / 23 do not compile in the
                                  reference (ecdsa.circom:31-37 reads past hashed[]). Others: PZK_E_PARAMS */
-  int32_t dg_hash_type;       /* DG_HASH_TYPE (160, 224, 256, 384) */
+  int32_t dg_hash_type;       /* DG_HASH_TYPE (160, 224, 256, 384; LIGHT: also 512) */
   int32_t document_type;      /* DOCUMENT_TYPE (1 = TD1, 3 = TD3) */
   int32_t ec_block_number;    /* EC_BLOCK_NUMBER */
   int32_t ec_shift;           /* EC_SHIFT (bits) */

@@ -58,6 +58,9 @@ hipError_t launch_qc_build(const PosConsts& K, fr* qc, hipStream_t st);
 hipError_t launch_smt_order(const fr* smt_core, uint32_t smt_core_fr, uint32_t* order, uint32_t batch, hipStream_t st);
 // QueryIdentity prep (query.hpp): DG1 fields, dg1 chunks, citizenship inverses, the query checks
 hipError_t launch_qry_prep(const DevLayout& L, const uint8_t* inputs, ValueStore vs, int32_t* status, hipStream_t st);
+// RegisterIdentityLight prep (light.hpp), after the SHA core: the dg1 chunks and the 248-bit dg1Hash value
+hipError_t launch_light_prep(const DevLayout& L, const uint8_t* inputs, const uint32_t* sha_core, ValueStore vs,
+                             int32_t* status, hipStream_t st);
 hipError_t launch_ec_core(const DevLayout& L, const uint8_t* inputs, const uint32_t* sha_core, uint64_t* ec_core,
                           uint64_t* ec_jac, fr* ec_inv, int32_t* status, uint32_t batch, hipStream_t st);
 hipError_t launch_emit_ecr(const DevLayout& L, const Work* work, uint32_t n_work, const Bufs& B, uint32_t batch,

@@ -206,6 +206,9 @@ struct RegInfo {
   int32_t q_dgf, q_cinv, q_cidx, q_nul;
   // QueryIdentityTD1 (document_type 1): 9 DG1 fields, dg1[760]; PoseidonHash(1) of documentNumber / personalNumber
   int32_t q_td1, q_doch, q_persh;
+  // RegisterIdentityLight (builder_light.cpp, light.hpp): the dg1Hash slot (the DG1 digest mod 2^248); it also uses
+  // j_dg1, in_dg1, dg1_chunk, v_dg1, v_sk, v_bjj
+  int32_t v_dg1hash;
 };
 
 // per-witness core sizes of the register-circuit kernels

@@ -575,7 +575,7 @@ static int pzk_instance_create_impl(const pzk_params* params, pzk_instance** out
   if (!rc) rc = upload(&I->d_loads, I->lay.loads);
   const bool chains = I->lay.is_register || I->lay.is_query;  // SMT / BabyJubJub chains
   if (!rc && chains) rc = upload(&I->d_level_task, level_task);
-  if (!rc && chains) {
+  if (!rc && (chains || I->lay.is_light)) {  // (RegisterIdentityLight: the BabyJubJub key, no SMT)
     if (hipMalloc(&I->d_bjj_table, sizeof(fr) * 3 * BJJ_TABLE_WINDOWS * 256) != hipSuccess ||
         launch_bjj_table(I->d_bjj_table, nullptr) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
       rc = fail(PZK_E_HIP, "BabyJubJub table setup failed");
@@ -756,7 +756,7 @@ static int ensure_scratch(pzk_instance* I, Scratch& S, size_t batch) {
       {(void**)&S.d_rsa_core, 8ull * L.rsa_core_words * batch},
       {(void**)&S.d_rsa_colsum, L.is_register ? 8ull * 3 * 2 * L.reg.K * batch : 0},
       {(void**)&S.d_bjj_core, 32ull * L.bjj_core_fr * batch},
-      {(void**)&S.d_bjj_scratch, (L.is_register || L.is_query) && bjj_uses_scratch() ? 32ull * BJJ_SCRATCH_FR * batch : 0},
+      {(void**)&S.d_bjj_scratch, (L.is_register || L.is_query || L.is_light) && bjj_uses_scratch() ? 32ull * BJJ_SCRATCH_FR * batch : 0},
       {(void**)&S.d_smt_core, 32ull * L.smt_core_fr * batch},
       {(void**)&S.d_ec_core, L.is_ecdsa ? 8ull * EC_GEO[L.reg.ec_curve].core_words * batch : 0},
       {(void**)&S.d_ec_jac, L.is_ecdsa ? 8ull * EC_GEO[L.reg.ec_curve].jac_words * batch : 0},
@@ -1020,6 +1020,36 @@ static int batch_locked(pzk_instance* I, const uint8_t* d_inputs, size_t batch, 
       if ((rc = emit(E_QRY, s_sha))) return rc;
       if ((rc = emit(E_BITS, s_sha))) return rc;
     }
+  } else if (lay.is_light) {
+    // RegisterIdentityLight (light.hpp): two chains that meet at the dg1 commitment. The call's chain
+    // stream: the BabyJubJub key and the sk hash (Poseidon level 0), then, once the other chain has ended, the dg1
+    // commitment and the pk identity hash (levels 1-2). The second high-priority stream: the SHA core and
+    // k_light_prep (the dg1 chunks, dg1Hash). The SHA emitters (over 90 % of the witness) on the SHA emitter stream behind
+    // the SHA core, everything else on the other emitter stream.
+    HIPCHK(hipEventRecord(I->ev_load, st));
+    HIPCHK(hipStreamWaitEvent(s_rsa, I->ev_load, 0));
+    { PhaseScope ps(T, slot, PH_SHA_CORE, s_rsa);
+      HIPCHK(launch_sha_core(L, d_inputs, S.d_derived, 0, L.n_sha, S.d_sha_core, d_status, B, s_rsa)); }
+    HIPCHK(hipEventRecord(I->ev_sha, s_rsa));
+    { PhaseScope ps(T, slot, PH_PREP, s_rsa); HIPCHK(launch_light_prep(L, d_inputs, S.d_sha_core, vs, d_status, s_rsa)); }
+    HIPCHK(hipEventRecord(I->ev_rsa, s_rsa));
+    { PhaseScope ps(T, slot, PH_BJJ_CORE, st);
+      HIPCHK(launch_bjj_core(L, vs, I->d_bjj_table, S.d_bjj_core, S.d_bjj_scratch, st)); }
+    HIPCHK(hipEventRecord(I->ev_bjj, st));
+    { PhaseScope ps(T, slot, PH_POS_CORE, st); if ((rc = pos_levels(0, 1))) return rc; }
+    HIPCHK(hipStreamWaitEvent(st, I->ev_rsa, 0));
+    { PhaseScope ps(T, slot, PH_POS_CORE, st); if ((rc = pos_levels(1, 1 << 20))) return rc; }
+    HIPCHK(hipEventRecord(I->ev_pos, st));
+    HIPCHK(hipStreamWaitEvent(s_sha, I->ev_sha, 0));
+    if ((rc = emit(E_SHA, s_sha))) return rc;
+    if ((rc = emit(E_SHA1, s_sha))) return rc;
+    if ((rc = emit(E_SHA5, s_sha))) return rc;
+    HIPCHK(hipStreamWaitEvent(s_emit, I->ev_bjj, 0));
+    if ((rc = emit(E_BJJ, s_emit))) return rc;
+    HIPCHK(hipStreamWaitEvent(s_emit, I->ev_pos, 0));  // (the chain stream has waited for the SHA chain by then)
+    if ((rc = emit(E_POS, s_emit))) return rc;
+    if ((rc = emit(E_BITS, s_emit))) return rc;
+    if ((rc = emit(E_GEN, s_emit))) return rc;
   } else if (!lay.is_register) {
     // standalone circuits: the core on the main stream; PoseidonHash(n)'s emitters on the emit stream behind it, so
     // call k's emitters run beside call k + 1's core (config 1 27.2M -> 28.7M witnesses/s); the SHA hashers' stay on
@@ -1407,6 +1437,7 @@ static int pzk_phase_info_impl(const pzk_instance* I, uint32_t phase, const char
   if (kernel) {
     *kernel = PHASE_KERNELS[phase];
     if (phase == PH_PREP && I->lay.is_query) *kernel = "k_qry_prep";
+    if (phase == PH_PREP && I->lay.is_light) *kernel = "k_light_prep";
     if (phase == PH_EMIT_SHA) {  // the SHA-2 and SHA-1 emitters share the phase: name the ones this instance runs
       const bool s2 = !I->lay.work[E_SHA].empty() || !I->lay.work[E_SHAD].empty(), s1 = !I->lay.work[E_SHA1].empty();
       const bool s5 = !I->lay.work[E_SHA5].empty() || !I->lay.work[E_SHA5D].empty();
@@ -1452,6 +1483,8 @@ static int pzk_phase_info_impl(const pzk_instance* I, uint32_t phase, const char
     if (phase == PH_PREP && L.is_query)  // k_qry_prep: the DG1 bits and the scalar inputs it reads (QI_EVID ..
       b += 32ull * (q_dg1_len(L.reg.q_td1) + QI_DG1) +  // QI_PKPASS) + the value slots written: DG1 fields, dg1
            32ull * (9 + 4 + 1 + 240);                   // chunks, citizenship index and its 240 IsEqual inverses
+    if (phase == PH_PREP && L.is_light)  // k_light_prep: the 4 x CH dg1 bits it reads, the digest words (at most
+      b += 32ull * 4 * L.reg.dg1_chunk + 64 + 32ull * 5;  // 64 B), the 4 chunk slots and the dg1Hash slot it writes
     if (phase == PH_SMT && (L.is_register || L.is_query))  // siblings, root and key read; SMT core and the
       b += 32ull * (SMT_LEVELS + 2) + 32ull * SMT_CORE_FR + 32ull * 2 * SMT_LEVELS;  // level hash inputs written
     if (phase == PH_RSA_CORE)  // core written + signature and modulus read; k_rsa_inv reads every remainder and the
