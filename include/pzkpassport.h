@@ -66,6 +66,13 @@ int pzk_passport_parse(const pzk_passport_src* src, pzk_passport_info* info);
 int pzk_passport_inputs(const pzk_params* params, const pzk_passport_src* srcs, size_t n, const uint8_t* identity,
                         uint8_t* rows, int32_t* status, int threads);
 
+/* The same, with the rows written packed (pzkwit.h, packed input rows): rows = n x row_bytes of
+ * pzk_packed_layout(params), for pzk_witness_batch_packed. Each row is written straight from the padded messages,
+ * the limbs and the identity elements: no full row is built on the way. Statuses and the zero row
+ * of a failed passport as above. */
+int pzk_passport_inputs_packed(const pzk_params* params, const pzk_passport_src* srcs, size_t n,
+                               const uint8_t* identity, uint8_t* rows, int32_t* status, int threads);
+
 #ifdef __cplusplus
 }
 #endif

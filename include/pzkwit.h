@@ -160,6 +160,42 @@ int pzk_instance_info(const pzk_instance* inst, pzk_info* info);
 int pzk_instance_input(const pzk_instance* inst, uint32_t i, const char** name, uint64_t* offset,
                        uint64_t* length);
 
+/* ---- Packed input rows ----
+ * A full input row spends 32 bytes on every input, though most inputs are one bit or one 64-bit limb. The
+ * packed row holds the same groups (pzk_instance_input), in the same order, each at a multiple of 16 bytes:
+ *   PZK_INPUT_BIT   n inputs in ceil(n / 8) bytes, input j = bit 7 - (j & 7) of byte j >> 3 (MSB first: a hashed
+ *                   message's padded bytes verbatim); pad bits are written 0 and ignored
+ *   PZK_INPUT_LIMB  8 bytes little-endian per input
+ *   PZK_INPUT_FIELD the 32 bytes verbatim (a scalar >= p stays representable and reports PZK_ST_INPUT_RANGE)
+ * every group and the row padded to a multiple of 16 bytes. The packed entry points expand the rows on the GPU
+ * (k_unpack_inputs) into the 32-byte rows every other kernel reads; the unpacked entry points are unchanged and
+ * remain the path for rows outside the packed domain (a non-bit in a BIT group, a limb >= 2^64). */
+enum { PZK_INPUT_BIT = 0, PZK_INPUT_LIMB = 1, PZK_INPUT_FIELD = 2 };
+
+/* Host-only: bytes per packed row of an instance, and the i-th group's kind, byte offset in the packed row and
+ * byte length (without the padding to 16). Groups are indexed as in pzk_instance_input. */
+int pzk_packed_layout(const pzk_params* params, uint64_t* row_bytes);
+int pzk_packed_group(const pzk_params* params, uint32_t i, uint32_t* kind, uint64_t* byte_offset,
+                     uint64_t* byte_length);
+/* The same for a live instance. */
+int pzk_instance_input_packed(const pzk_instance* inst, uint32_t i, uint32_t* kind, uint64_t* byte_offset,
+                              uint64_t* byte_length);
+
+/* Host: pack n full rows (n x n_inputs x 32 B) into packed rows (n x row_bytes) on `threads` host threads
+ * (<= 0: all this process may use). status = n x int32 (may be NULL): 0, or 1 for a row that has no packed form
+ * (a BIT input other than 0 / 1, a LIMB input >= 2^64); such a row's packed row is zero-filled, and the row
+ * stays on the unpacked path, where the GPU flags it. */
+int pzk_pack_inputs(const pzk_params* params, const uint8_t* rows, size_t n, uint8_t* packed, int32_t* status,
+                    int threads);
+/* Host: the inverse, packed rows -> full rows (n x n_inputs x 32 B). The CPU reference of the GPU kernel. */
+int pzk_unpack_inputs_host(const pzk_params* params, const uint8_t* packed, size_t n, uint8_t* rows);
+
+/* Device packed rows (batch x row_bytes, 16-byte aligned) -> caller-owned device full rows (batch x n_inputs x
+ * 32 B, 16-byte aligned), on exec->stream (NULL: the instance's main stream; complete after pzk_instance_sync or
+ * PZK_EXEC_SYNC). A caller that reuses inputs expands them once and calls pzk_witness_batch on the rows. */
+int pzk_unpack_inputs(pzk_instance* inst, const uint8_t* d_packed, size_t batch, uint8_t* d_rows,
+                      const pzk_exec* exec);
+
 /* The 76-byte .wtns header (wtns v2, 2 sections, n8 = 32, prime, witnessSize) that
  * calculateWTNSBin prepends. */
 int pzk_wtns_header(const pzk_instance* inst, uint8_t header[76]);
@@ -185,6 +221,15 @@ int pzk_instance_sync(pzk_instance* inst);
 /* Host-buffer convenience (copies in/out; used by the single-input calculateWitness path). */
 int pzk_witness_batch_host(pzk_instance* inst, const uint8_t* h_inputs, size_t batch, uint8_t* h_wtns,
                            int32_t* h_status, const pzk_exec* exec);
+
+/* pzk_witness_batch / pzk_witness_batch_host on packed rows (d_packed / h_packed: batch x row_bytes of
+ * pzk_packed_layout; device pointer 16-byte aligned). Same contract: stream semantics, pipelining over the scratch
+ * sets, batch limit, statuses. The rows are expanded into the call's scratch set first (allocated at an instance's
+ * first packed call), on the call's chain stream, and every kernel then runs as in the unpacked call. */
+int pzk_witness_batch_packed(pzk_instance* inst, const uint8_t* d_packed, size_t batch, uint8_t* d_wtns,
+                             size_t wtns_stride, int32_t* d_status, const pzk_exec* exec);
+int pzk_witness_batch_host_packed(pzk_instance* inst, const uint8_t* h_packed, size_t batch, uint8_t* h_wtns,
+                                  int32_t* h_status, const pzk_exec* exec);
 
 /* Streamed delivery to host memory (replaces gen-witness.sh's one generate_witness.js + .wtns write per
  * input, circuits/scripts/gen-witness.sh:25, for a whole batch): h_inputs = batch x n_inputs x 32 B (host);

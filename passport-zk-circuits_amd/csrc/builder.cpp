@@ -172,7 +172,7 @@ bool build_sha256(const pzk_params& p, Layout& L, std::string& why) {
   Builder b(L);
   L.n_inputs = 512ull * B;
   L.n_outputs = 256;
-  L.inputs.push_back({"in", 0, L.n_inputs});
+  L.inputs.push_back({"in", 0, L.n_inputs, IK_BIT});  // the SHA core reads bits
   b.region(RK_ONE, 1);
   b.sha256(0, B, false);
   b.finalize();
@@ -185,7 +185,7 @@ bool build_sha1(const pzk_params& p, Layout& L, std::string& why) {
   Builder b(L);
   L.n_inputs = 512ull * B;
   L.n_outputs = 160;
-  L.inputs.push_back({"in", 0, L.n_inputs});
+  L.inputs.push_back({"in", 0, L.n_inputs, IK_BIT});  // the SHA core reads bits
   b.region(RK_ONE, 1);
   b.sha1(0, B);
   b.finalize();
@@ -198,7 +198,7 @@ bool build_sha512(const pzk_params& p, Layout& L, std::string& why, int O) {
   Builder b(L);
   L.n_inputs = 1024ull * B;
   L.n_outputs = O;
-  L.inputs.push_back({"in", 0, L.n_inputs});
+  L.inputs.push_back({"in", 0, L.n_inputs, IK_BIT});  // the SHA core reads bits
   b.region(RK_ONE, 1);
   b.sha512(0, B, O);
   b.finalize();

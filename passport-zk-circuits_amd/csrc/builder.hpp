@@ -16,9 +16,15 @@
 
 namespace pzk {
 
+// How the core kernels read a group, which is what its packed form (unpack.hpp) may drop: BIT = bit
+// reads that flag anything but 0 / 1 (in_bit, the SHA cores), LIMB = in_u64 behind an in_is_u64 check, FIELD =
+// load_fr of all 32 bytes (the default: nothing dropped).
+enum InputKind : uint32_t { IK_BIT = PZK_INPUT_BIT, IK_LIMB = PZK_INPUT_LIMB, IK_FIELD = PZK_INPUT_FIELD };
+
 struct InputGroup {
   std::string name;
   uint64_t offset, length;
+  InputKind kind = IK_FIELD;
 };
 
 struct Layout {

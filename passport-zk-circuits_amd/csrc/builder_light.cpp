@@ -32,7 +32,7 @@ bool build_light(const pzk_params& p, Layout& L, std::string& why) {
   L.n_inputs = 1025;
   L.n_outputs = 3;
   L.n_public = 0;
-  L.inputs = {{"dg1", (uint64_t)IN_DG1, 1024}, {"skIdentity", (uint64_t)IN_SK, 1}};
+  L.inputs = {{"dg1", (uint64_t)IN_DG1, 1024, IK_BIT}, {"skIdentity", (uint64_t)IN_SK, 1}};
   L.is_light = true;
   L.params = p;
   L.bjj_core_fr = BJJ_CORE_FR;

@@ -49,7 +49,7 @@ bool build_query(const pzk_params& p, Layout& L, std::string& why) {
               {"citizenshipMask", QI_CMASK, 1},
               {"skIdentity", QI_SK, 1},
               {"pkPassportHash", QI_PKPASS, 1},
-              {"dg1", QI_DG1, (uint64_t)DG1L},
+              {"dg1", QI_DG1, (uint64_t)DG1L, IK_BIT},  // (the small scalars stay FIELD: their Num2Bits / range checks)
               {"idStateSiblings", (uint64_t)IN_SIB, (uint64_t)Q_DEPTH},
               {"timestamp", (uint64_t)IN_TS, 1},
               {"identityCounter", (uint64_t)IN_IC, 1}};

@@ -112,10 +112,16 @@ bool build_register(const pzk_params& p, Layout& L, std::string& why) {
   L.n_inputs = IN_SK + 1;
   L.n_outputs = 4;
   L.n_public = 1;
-  L.inputs = {{"slaveMerkleRoot", (uint64_t)IN_ROOT, 1},   {"encapsulatedContent", (uint64_t)IN_EC, (uint64_t)ecLen},
-              {"dg1", (uint64_t)IN_DG1, 1024},             {"dg15", (uint64_t)IN_DG15, (uint64_t)d15Len},
-              {"signedAttributes", (uint64_t)IN_SA, 1024},  {"signature", (uint64_t)IN_SIG, (uint64_t)K},
-              {"pubkey", (uint64_t)IN_PK, (uint64_t)K},     {"slaveMerkleInclusionBranches", (uint64_t)IN_BR, 80},
+  // kinds (builder.hpp InputKind): the four hashed messages are read as bits by the SHA cores, k_prep and the flow
+  // (in_bit: a non-bit flags); signature and pubkey as limbs behind in_is_u64 by the RSA / EC cores and k_prep
+  L.inputs = {{"slaveMerkleRoot", (uint64_t)IN_ROOT, 1},
+              {"encapsulatedContent", (uint64_t)IN_EC, (uint64_t)ecLen, IK_BIT},
+              {"dg1", (uint64_t)IN_DG1, 1024, IK_BIT},
+              {"dg15", (uint64_t)IN_DG15, (uint64_t)d15Len, IK_BIT},
+              {"signedAttributes", (uint64_t)IN_SA, 1024, IK_BIT},
+              {"signature", (uint64_t)IN_SIG, (uint64_t)K, IK_LIMB},
+              {"pubkey", (uint64_t)IN_PK, (uint64_t)K, IK_LIMB},
+              {"slaveMerkleInclusionBranches", (uint64_t)IN_BR, 80},
               {"skIdentity", (uint64_t)IN_SK, 1}};
   L.is_register = true;
   L.params = p;

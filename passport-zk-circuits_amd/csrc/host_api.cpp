@@ -1,7 +1,10 @@
 // Host-only half of the C-ABI (host_api.hpp).
 #include <string.h>
 
+#include <sched.h>
+
 #include <algorithm>
+#include <thread>
 
 #include "../../include/pzkwit.h"
 #include "host_api.hpp"
@@ -129,6 +132,75 @@ void map_program(const Layout& lay, const std::vector<uint32_t>& inv, bool force
   if (out.mprog.empty()) out.mprog.push_back(0);
 }
 
+bool packed_layout(const Layout& lay, PackedLayout& out, std::string& why) {
+  out = PackedLayout();
+  if (lay.inputs.empty() || lay.inputs.size() > UNPACK_MAX_GROUPS) { why = "internal: input group count"; return false; }
+  uint64_t el = 0, by = 0;
+  for (const InputGroup& g : lay.inputs) {
+    if (g.offset != el || g.kind > IK_FIELD) { why = "internal: input groups do not tile the row"; return false; }
+    out.groups.push_back(PackedGroup{(uint32_t)g.offset, (uint32_t)g.length, (uint32_t)g.kind, (uint32_t)by});
+    el += g.length;
+    by += (packed_group_bytes(g.kind, g.length) + 15) & ~15ull;
+  }
+  if (el != lay.n_inputs || el >> 31 || by >> 32) { why = "internal: input groups do not tile the row"; return false; }
+  out.row_bytes = by;
+  return true;
+}
+
+bool pack_row(const PackedLayout& P, const uint8_t* row, uint8_t* packed) {
+  memset(packed, 0, P.row_bytes);
+  auto high_zero = [](const uint8_t* e, int from) {
+    uint8_t acc = 0;
+    for (int k = from; k < 32; k++) acc |= e[k];
+    return acc == 0;
+  };
+  for (const PackedGroup& g : P.groups) {
+    const uint8_t* src = row + 32ull * g.elem_off;
+    uint8_t* dst = packed + g.byte_off;
+    bool ok = true;
+    if (g.kind == IK_FIELD) {
+      memcpy(dst, src, 32ull * g.elem_len);
+    } else if (g.kind == IK_LIMB) {
+      for (uint32_t j = 0; j < g.elem_len && ok; j++) {
+        ok = high_zero(src + 32ull * j, 8);
+        memcpy(dst + 8ull * j, src + 32ull * j, 8);
+      }
+    } else {
+      for (uint32_t j = 0; j < g.elem_len && ok; j++) {
+        const uint8_t* e = src + 32ull * j;
+        ok = e[0] <= 1 && high_zero(e, 1);
+        dst[j >> 3] |= (uint8_t)((e[0] & 1) << (7 - (j & 7)));
+      }
+    }
+    if (!ok) { memset(packed, 0, P.row_bytes); return false; }
+  }
+  return true;
+}
+
+void unpack_row(const PackedLayout& P, uint64_t n_inputs, const uint8_t* packed, uint8_t* row) {
+  memset(row, 0, 32ull * n_inputs);
+  for (const PackedGroup& g : P.groups) {
+    const uint8_t* src = packed + g.byte_off;
+    uint8_t* dst = row + 32ull * g.elem_off;
+    if (g.kind == IK_FIELD) memcpy(dst, src, 32ull * g.elem_len);
+    else if (g.kind == IK_LIMB)
+      for (uint32_t j = 0; j < g.elem_len; j++) memcpy(dst + 32ull * j, src + 8ull * j, 8);
+    else
+      for (uint32_t j = 0; j < g.elem_len; j++) dst[32ull * j] = (src[j >> 3] >> (7 - (j & 7))) & 1;
+  }
+}
+
+// host threads of a bulk call: `threads`, or (<= 0) the CPUs this process may run on, at most one per item
+static int host_threads(int threads, size_t n) {
+  int nt = threads;
+  if (nt <= 0) {
+    cpu_set_t cs;
+    nt = sched_getaffinity(0, sizeof cs, &cs) == 0 ? CPU_COUNT(&cs) : (int)std::thread::hardware_concurrency();
+    nt = std::max(nt, 1);
+  }
+  return (int)std::min<size_t>((size_t)nt, std::max<size_t>(n, 1));
+}
+
 }  // namespace pzk
 
 using namespace pzk;
@@ -172,6 +244,82 @@ static int layout_region_impl(const pzk_params* params, uint32_t i, uint64_t* of
   if (len) *len = L.regions[i].len;
   if (kind) *kind = L.regions[i].kind;
   return 0;
+}
+
+static int packed_of(const pzk_params* params, Layout& L, PackedLayout& P) {
+  if (!params) return api_fail(PZK_E_ARG, "null argument");
+  std::string why;
+  if (!build_layout(*params, L, why)) return api_fail(PZK_E_PARAMS, why);
+  if (!packed_layout(L, P, why)) return api_fail(PZK_E_PARAMS, why);
+  return 0;
+}
+
+static int packed_layout_impl(const pzk_params* params, uint64_t* row_bytes) {
+  Layout L;
+  PackedLayout P;
+  if (int rc = packed_of(params, L, P)) return rc;
+  if (row_bytes) *row_bytes = P.row_bytes;
+  return 0;
+}
+
+static int packed_group_impl(const pzk_params* params, uint32_t i, uint32_t* kind, uint64_t* off, uint64_t* len) {
+  Layout L;
+  PackedLayout P;
+  if (int rc = packed_of(params, L, P)) return rc;
+  if (i >= P.groups.size()) return api_fail(PZK_E_ARG, "input index out of range");
+  if (kind) *kind = P.groups[i].kind;
+  if (off) *off = P.groups[i].byte_off;
+  if (len) *len = packed_group_bytes(P.groups[i].kind, P.groups[i].elem_len);
+  return 0;
+}
+
+static int pack_inputs_impl(const pzk_params* params, const uint8_t* rows, size_t n, uint8_t* packed, int32_t* status,
+                            int threads) {
+  if (n && (!rows || !packed)) return api_fail(PZK_E_ARG, "null argument");
+  Layout L;
+  PackedLayout P;
+  if (int rc = packed_of(params, L, P)) return rc;
+  const size_t in_row = 32ull * L.n_inputs;
+  auto work = [&](size_t i) {
+    const bool ok = pack_row(P, rows + in_row * i, packed + P.row_bytes * i);
+    if (status) status[i] = ok ? 0 : 1;
+  };
+  const int nt = host_threads(threads, n);
+  if (nt <= 1) {
+    for (size_t i = 0; i < n; i++) work(i);
+    return 0;
+  }
+  std::vector<std::thread> pool;
+  for (int t = 0; t < nt; t++)
+    pool.emplace_back([&, t]() { for (size_t i = t; i < n; i += (size_t)nt) work(i); });
+  for (auto& th : pool) th.join();
+  return 0;
+}
+
+static int unpack_inputs_host_impl(const pzk_params* params, const uint8_t* packed, size_t n, uint8_t* rows) {
+  if (n && (!rows || !packed)) return api_fail(PZK_E_ARG, "null argument");
+  Layout L;
+  PackedLayout P;
+  if (int rc = packed_of(params, L, P)) return rc;
+  for (size_t i = 0; i < n; i++) unpack_row(P, L.n_inputs, packed + P.row_bytes * i, rows + 32ull * L.n_inputs * i);
+  return 0;
+}
+
+int pzk_packed_layout(const pzk_params* params, uint64_t* row_bytes) {
+  return guarded([&] { return packed_layout_impl(params, row_bytes); });
+}
+
+int pzk_packed_group(const pzk_params* params, uint32_t i, uint32_t* kind, uint64_t* byte_offset, uint64_t* byte_length) {
+  return guarded([&] { return packed_group_impl(params, i, kind, byte_offset, byte_length); });
+}
+
+int pzk_pack_inputs(const pzk_params* params, const uint8_t* rows, size_t n, uint8_t* packed, int32_t* status,
+                    int threads) {
+  return guarded([&] { return pack_inputs_impl(params, rows, n, packed, status, threads); });
+}
+
+int pzk_unpack_inputs_host(const pzk_params* params, const uint8_t* packed, size_t n, uint8_t* rows) {
+  return guarded([&] { return unpack_inputs_host_impl(params, packed, n, rows); });
 }
 
 int pzk_sym_check(const pzk_params* params, const char* sym, size_t sym_len, uint64_t* witness_size) {

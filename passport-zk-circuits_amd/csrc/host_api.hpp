@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "builder.hpp"
+#include "unpack.hpp"
 
 namespace pzk {
 
@@ -37,6 +38,20 @@ struct MapProgram {
   uint32_t pos_nomix = 0;           // bit t: no kept signal of a width-t Poseidon block reads a GetSum row (pos_prog.hpp)
 };
 void map_program(const Layout& lay, const std::vector<uint32_t>& inv, bool force_gather, MapProgram& out);
+
+// The packed input row of a layout (include/pzkwit.h): one PackedGroup per input group, in flat-input
+// order, every group at a multiple of 16 bytes, the row a multiple of 16 bytes. false (why set): the groups do not tile
+// [0, n_inputs) in order, or there are more than UNPACK_MAX_GROUPS. A group may be empty (dg15 without active
+// authentication): it takes no bytes.
+struct PackedLayout {
+  std::vector<PackedGroup> groups;
+  uint64_t row_bytes = 0;
+};
+bool packed_layout(const Layout& lay, PackedLayout& out, std::string& why);
+// one full row (32 B per input) -> its packed row; false (packed row zero-filled): a BIT input other than 0 / 1, or
+// a LIMB input >= 2^64
+bool pack_row(const PackedLayout& P, const uint8_t* row, uint8_t* packed);
+void unpack_row(const PackedLayout& P, uint64_t n_inputs, const uint8_t* packed, uint8_t* row);
 
 // Exceptions never cross the C ABI (pzkwit.h: every function returns 0 or a negative PZK_E_* code): each entry point
 // runs its implementation under guarded(), which maps a host allocation failure to PZK_E_NOMEM and any other

@@ -936,40 +936,88 @@ extern "C" int pzk_passport_parse(const pzk_passport_src* src, pzk_passport_info
   }
 }
 
-extern "C" int pzk_passport_inputs(const pzk_params* params, const pzk_passport_src* srcs, size_t n, const uint8_t* identity,
-                                   uint8_t* rows, int32_t* status, int threads) {
-  if (!params || (n && (!srcs || !rows || !status))) return pzk::api_fail(PZK_E_ARG, "pzk_passport_inputs: null argument");
-  if (params->circuit != PZK_CIRCUIT_REGISTER) return pzk::api_fail(PZK_E_PARAMS, "pzk_passport_inputs: not a register instance");
-  pzk_info li{};
-  uint32_t nreg = 0;
-  if (int rc = pzk_layout_query(params, &li, &nreg)) return rc;
+namespace {
+
+// One passport's groups (bits, limbs, identity elements) for an instance of `params`, or the status it fails with.
+// Shared by the full-row and the packed-row writers below.
+struct RowShape {
+  int sig, K;
+  size_t ecL, d15L, n_in;
+};
+
+// 0, or the layout query's error / PZK_E_PARAMS (`who` names the entry point in the message)
+int row_shape(const pzk_params* params, RowShape& S, const char* who) {
   const int sig = params->signature_type;
   // limbs per coordinate: CHUNK_NUMBER of the circuit (registerIdentityBuilder.circom:59-99; 7 x 32 bits for SIG 24,
   // where processPassport's getChunkedParams (:590-626) makes 4 x 64: such rows get PZK_PP_LIMBS)
   const int K = sig == 24 ? 7 : sig == 25 ? 6 : sig >= 20 ? 4 : sig == 2 ? 64 : (sig == 4 || sig == 14) ? 48 : 32;
   const int hb = (sig == 13 || sig == 25) ? 1024 : 512;  // HASH_BLOCK_SIZE (registerIdentityBuilder.circom:104-111)
-  const size_t ecL = (size_t)params->ec_block_number * hb, d15L = (size_t)params->dg15_block_number * hb;
-  const size_t n_in = 1 + ecL + 1024 + d15L + 1024 + 2 * (size_t)(sig >= 20 ? 2 * K : K) + 80 + 1;
-  if (n_in != li.n_inputs) return pzk::api_fail(PZK_E_PARAMS, "pzk_passport_inputs: input layout mismatch");
-  const size_t row_bytes = 32 * n_in;
+  S.sig = sig;
+  S.K = K;
+  S.ecL = (size_t)params->ec_block_number * hb;
+  S.d15L = (size_t)params->dg15_block_number * hb;
+  S.n_in = 1 + S.ecL + 1024 + S.d15L + 1024 + 2 * (size_t)(sig >= 20 ? 2 * K : K) + 80 + 1;
+  pzk_info li{};
+  uint32_t nreg = 0;
+  if (int rc = pzk_layout_query(params, &li, &nreg)) return rc;
+  if (S.n_in != li.n_inputs) return pzk::api_fail(PZK_E_PARAMS, std::string(who) + ": input layout mismatch");
+  return 0;
+}
+
+// PZK_PP_OK, or why the parsed passport does not fit the instance
+int fits(const pzk_params* params, const RowShape& S, const Parsed& P) {
+  if (P.info.params.signature_type == 0) return PZK_PP_UNKNOWN;
+  pzk_params want = *params, got = P.info.params;
+  want.size_arg = got.size_arg = 0;
+  if (std::memcmp(&want, &got, sizeof want)) return PZK_PP_PARAMS;
+  const int coords = S.sig >= 20 ? 2 : 1;
+  if (P.info.chunk_bits != (S.sig == 24 ? 32 : 64) || P.info.chunk_number != S.K || (int)P.pk_limbs.size() != coords * S.K)
+    return PZK_PP_LIMBS;
+  if (P.ec_bits.size() != S.ecL || P.dg1_bits.size() != 1024 || P.dg15_bits.size() != S.d15L || P.sa_bits.size() != 1024)
+    return PZK_PP_SIZE;
+  return PZK_PP_OK;
+}
+
+// bits (one per byte) -> MSB-first bytes: the packed BIT group (pzkwit.h)
+void pack_bits(uint8_t* dst, const std::vector<uint8_t>& bits) {
+  for (size_t j = 0; j < bits.size(); j++) dst[j >> 3] |= (uint8_t)((bits[j] & 1) << (7 - (j & 7)));
+}
+
+template <typename W>
+int run_rows(size_t n, int threads, W work) {
+  int nt = threads;
+  if (nt <= 0) {  // the CPUs this process may run on (a container's share, not the machine's count)
+    cpu_set_t cs;
+    nt = sched_getaffinity(0, sizeof cs, &cs) == 0 ? CPU_COUNT(&cs) : (int)std::thread::hardware_concurrency();
+    nt = std::max(nt, 1);
+  }
+  nt = (int)std::min<size_t>((size_t)nt, std::max<size_t>(n, 1));
+  if (nt <= 1) {
+    for (size_t i = 0; i < n; i++) work(i);
+    return 0;
+  }
+  std::vector<std::thread> pool;
+  for (int t = 0; t < nt; t++)
+    pool.emplace_back([&, t]() { for (size_t i = t; i < n; i += (size_t)nt) work(i); });
+  for (auto& th : pool) th.join();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int pzk_passport_inputs(const pzk_params* params, const pzk_passport_src* srcs, size_t n, const uint8_t* identity,
+                                   uint8_t* rows, int32_t* status, int threads) {
+  if (!params || (n && (!srcs || !rows || !status))) return pzk::api_fail(PZK_E_ARG, "pzk_passport_inputs: null argument");
+  if (params->circuit != PZK_CIRCUIT_REGISTER) return pzk::api_fail(PZK_E_PARAMS, "pzk_passport_inputs: not a register instance");
+  RowShape S;
+  if (int rc = row_shape(params, S, "pzk_passport_inputs")) return rc;
+  const size_t row_bytes = 32 * S.n_in;
   auto work = [&](size_t i) {
     uint8_t* row = rows + row_bytes * i;
     std::memset(row, 0, row_bytes);
     try {
       const Parsed P = process(srcs[i]);
-      if (P.info.params.signature_type == 0) { status[i] = PZK_PP_UNKNOWN; return; }
-      pzk_params want = *params, got = P.info.params;
-      want.size_arg = got.size_arg = 0;
-      if (std::memcmp(&want, &got, sizeof want)) { status[i] = PZK_PP_PARAMS; return; }
-      const int coords = sig >= 20 ? 2 : 1;
-      if (P.info.chunk_bits != (sig == 24 ? 32 : 64) || P.info.chunk_number != K || (int)P.pk_limbs.size() != coords * K) {
-        status[i] = PZK_PP_LIMBS;
-        return;
-      }
-      if (P.ec_bits.size() != ecL || P.dg1_bits.size() != 1024 || P.dg15_bits.size() != d15L || P.sa_bits.size() != 1024) {
-        status[i] = PZK_PP_SIZE;
-        return;
-      }
+      if ((status[i] = fits(params, S, P)) != PZK_PP_OK) return;
       const uint8_t* id = identity ? identity + (size_t)82 * 32 * i : nullptr;
       size_t o = 0;
       if (id) std::memcpy(row, id, 32);  // slaveMerkleRoot
@@ -992,20 +1040,69 @@ extern "C" int pzk_passport_inputs(const pzk_params* params, const pzk_passport_
       status[i] = PZK_PP_PARSE;
     }
   };
-  int nt = threads;
-  if (nt <= 0) {  // the CPUs this process may run on (a container's share, not the machine's count)
-    cpu_set_t cs;
-    nt = sched_getaffinity(0, sizeof cs, &cs) == 0 ? CPU_COUNT(&cs) : (int)std::thread::hardware_concurrency();
-    nt = std::max(nt, 1);
+  return run_rows(n, threads, work);
+}
+
+// The packed rows, written group by group at the offsets of pzk_packed_group: the padded messages' bits into MSB-first
+// bytes, 8 bytes per limb, the identity elements verbatim. No full row is built.
+static int passport_inputs_packed_impl(const pzk_params* params, const pzk_passport_src* srcs, size_t n,
+                                       const uint8_t* identity, uint8_t* rows, int32_t* status, int threads) {
+  if (!params || (n && (!srcs || !rows || !status)))
+    return pzk::api_fail(PZK_E_ARG, "pzk_passport_inputs_packed: null argument");
+  if (params->circuit != PZK_CIRCUIT_REGISTER)
+    return pzk::api_fail(PZK_E_PARAMS, "pzk_passport_inputs_packed: not a register instance");
+  RowShape S;
+  if (int rc = row_shape(params, S, "pzk_passport_inputs_packed")) return rc;
+  // groups: root, ec, dg1, dg15, sa, signature, pubkey, branches, sk
+  uint64_t row_bytes = 0, off[9], len[9];
+  if (int rc = pzk_packed_layout(params, &row_bytes)) return rc;
+  const int coords = S.sig >= 20 ? 2 : 1;
+  const uint64_t want[9] = {32, (S.ecL + 7) / 8, 128, (S.d15L + 7) / 8, 128, 8ull * coords * S.K, 8ull * coords * S.K, 80 * 32, 32};
+  for (uint32_t g = 0; g < 9; g++) {
+    uint32_t kind;
+    if (int rc = pzk_packed_group(params, g, &kind, &off[g], &len[g])) return rc;
+    if (len[g] != want[g] || off[g] + len[g] > row_bytes)
+      return pzk::api_fail(PZK_E_PARAMS, "pzk_passport_inputs_packed: packed layout mismatch");
   }
-  nt = (int)std::min<size_t>((size_t)nt, std::max<size_t>(n, 1));
-  if (nt <= 1) {
-    for (size_t i = 0; i < n; i++) work(i);
-    return 0;
+  auto work = [&](size_t i) {
+    uint8_t* row = rows + row_bytes * i;
+    std::memset(row, 0, row_bytes);
+    try {
+      const Parsed P = process(srcs[i]);
+      if ((status[i] = fits(params, S, P)) != PZK_PP_OK) return;
+      const uint8_t* id = identity ? identity + (size_t)82 * 32 * i : nullptr;
+      if (id) std::memcpy(row + off[0], id, 32);  // slaveMerkleRoot
+      pack_bits(row + off[1], P.ec_bits);
+      pack_bits(row + off[2], P.dg1_bits);
+      pack_bits(row + off[3], P.dg15_bits);
+      pack_bits(row + off[4], P.sa_bits);
+      const size_t nl = (size_t)coords * S.K;  // (both lists have chunk_number limbs per coordinate)
+      for (size_t k = 0; k < std::min(P.sig_limbs.size(), nl); k++) std::memcpy(row + off[5] + 8 * k, P.sig_limbs[k].data(), 8);
+      for (size_t k = 0; k < std::min(P.pk_limbs.size(), nl); k++) std::memcpy(row + off[6] + 8 * k, P.pk_limbs[k].data(), 8);
+      if (id) std::memcpy(row + off[7], id + 64, 80 * 32);  // slaveMerkleInclusionBranches
+      if (id) std::memcpy(row + off[8], id + 32, 32);       // skIdentity
+      status[i] = PZK_PP_OK;
+    } catch (const Fail& e) {
+      std::memset(row, 0, row_bytes);
+      status[i] = e.code;
+    } catch (const std::exception&) {
+      std::memset(row, 0, row_bytes);
+      status[i] = PZK_PP_PARSE;
+    }
+  };
+  return run_rows(n, threads, work);
+}
+
+// (host_api.hpp's guarded(), restated: this unit is also built without the HIP headers, tools/fuzz/passport_fuzz.cpp)
+extern "C" int pzk_passport_inputs_packed(const pzk_params* params, const pzk_passport_src* srcs, size_t n,
+                                          const uint8_t* identity, uint8_t* rows, int32_t* status, int threads) {
+  try {
+    return passport_inputs_packed_impl(params, srcs, n, identity, rows, status, threads);
+  } catch (const std::bad_alloc&) {
+    return pzk::api_fail(PZK_E_NOMEM, "host memory allocation failed");
+  } catch (const std::exception& e) {
+    return pzk::api_fail(PZK_E_ARG, std::string("internal error: ") + e.what());
+  } catch (...) {
+    return pzk::api_fail(PZK_E_ARG, "internal error");
   }
-  std::vector<std::thread> pool;
-  for (int t = 0; t < nt; t++)
-    pool.emplace_back([&, t]() { for (size_t i = t; i < n; i += (size_t)nt) work(i); });
-  for (auto& th : pool) th.join();
-  return 0;
 }

@@ -120,9 +120,12 @@ struct Scratch {
   uint8_t* d_ec_tab = nullptr;
   uint8_t* d_derived = nullptr;  // RSA-PSS derived SHA messages
   uint32_t* d_smt_order = nullptr;  // witnesses by SMT insertion level, deepest first (k_smt_order)
+  // packed calls only (ensure_in_rows): the call's expanded input rows, with their own capacity
+  uint8_t* d_in_rows = nullptr;
+  size_t in_cap = 0;
   void free_all() {
     void* ptrs[] = {d_sha_core, d_pos_core, d_values, d_rsa_core, d_rsa_colsum, d_bjj_core, d_bjj_scratch,
-                    d_smt_core, d_ec_core, d_ec_jac, d_ec_inv, d_ec_tab, d_derived, d_smt_order};
+                    d_smt_core, d_ec_core, d_ec_jac, d_ec_inv, d_ec_tab, d_derived, d_smt_order, d_in_rows};
     for (void* p : ptrs)
       if (p) (void)hipFree(p);
     *this = Scratch();
@@ -256,6 +259,9 @@ struct pzk_instance {
   }
   uint8_t* d_o0[2] = {};
   size_t o0_cap = 0;
+  // packed input rows (unpack.hpp): the group table, and its device copy from the first packed call on
+  PackedLayout packed;
+  PackedGroup* d_packed_groups = nullptr;
   // staging for the host-buffer path
   size_t host_cap = 0;
   uint8_t *d_in = nullptr, *d_out = nullptr;
@@ -487,7 +493,8 @@ static void free_all(pzk_instance* I) {
   void* ptrs[] = {I->d_regions, I->d_gen_pieces, I->d_sha_prog, I->d_pos_prog, I->d_sha, I->d_pos, I->d_loads, I->d_level_task,
                   I->d_pos_consts, I->d_bjj_table, I->d_in, I->d_out, I->d_status, I->d_ec_gpow, I->d_ec_prog,
                   I->d_ec_tab_off, I->d_ec_ops[0], I->d_ec_ops[1], I->d_ec_ops[2], I->d_inv_small, I->d_map,
-                  I->d_o0[0], I->d_o0[1], I->d_keep_bits, I->d_keep_rank, I->d_mprog, I->d_pos_zimg, I->d_qc};
+                  I->d_o0[0], I->d_o0[1], I->d_keep_bits, I->d_keep_rank, I->d_mprog, I->d_pos_zimg, I->d_qc,
+                  I->d_packed_groups};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto* p : I->d_work)
@@ -559,6 +566,7 @@ static int pzk_instance_create_impl(const pzk_params* params, pzk_instance** out
   I->nsets = nsets_env(params->circuit == PZK_CIRCUIT_QUERY);
   std::string why;
   if (!build_layout(*params, I->lay, why)) { delete I; return fail(PZK_E_PARAMS, why); }
+  if (!packed_layout(I->lay, I->packed, why)) { delete I; return fail(PZK_E_PARAMS, why); }
   HIPCHK(hipGetDevice(&I->device));
   int rc;
   if ((rc = load_poseidon(I)) != 0) { free_all(I); delete I; return rc; }
@@ -774,6 +782,30 @@ static int ensure_scratch(pzk_instance* I, Scratch& S, size_t batch) {
   return 0;
 }
 
+// A packed call's device state, made at the instance's first packed call (an instance that never makes one allocates
+// nothing here): the group table, and the scratch set's expanded rows. Growing the rows drains the instance first:
+// an earlier call in flight may still read them.
+static int ensure_in_rows(pzk_instance* I, Scratch* S, size_t batch) {
+  if (!I->d_packed_groups) {
+    int rc = upload(&I->d_packed_groups, I->packed.groups);
+    if (rc) return rc;
+  }
+  if (!S || batch <= S->in_cap) return 0;
+  if (S->d_in_rows) {
+    int rc = sync_all(I);
+    if (rc) return rc;
+    (void)hipFree(S->d_in_rows);
+    S->d_in_rows = nullptr;
+    S->in_cap = 0;
+  }
+  if (hipMalloc(&S->d_in_rows, 32ull * I->lay.n_inputs * batch) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PZK_E_NOMEM, "device allocation of the expanded input rows failed");
+  }
+  S->in_cap = batch;
+  return 0;
+}
+
 static int check_exec_device(const pzk_instance* I, const pzk_exec* exec) {
   if (exec && exec->device >= 0 && exec->device != I->device)
     return fail(PZK_E_ARG, "pzk_exec.device " + std::to_string(exec->device) + " != the instance's device " +
@@ -885,14 +917,24 @@ static int ensure_chain_streams(pzk_instance* I) {
 // the staging-slot waits of batch_mapped). Every stream of the call descends from its chain stream st (the
 // other streams wait for events recorded on st), so st waiting for dep orders the whole call after it — also
 // when a QueryIdentity call's chain runs on s_rsa or s_tail instead of the main stream.
+// d_packed: the call's inputs as packed rows (then d_inputs is null): k_unpack_inputs expands them into the scratch
+// set's d_in_rows on st, behind the ev_done[set], entry and dep waits and before k_load_values, and the call runs
+// unchanged on those rows. Every reader of the rows (cores, and the emitters that copy inputs) is on a stream that
+// descends from st, and the set is taken again only after ev_done[set] on all streams, so the rows outlive their
+// last reader and the next expansion into them follows it.
 static int batch_locked(pzk_instance* I, const uint8_t* d_inputs, size_t batch, uint8_t* d_wtns, size_t stride,
-                        int32_t* d_status, const pzk_exec* exec, hipStream_t dep = nullptr) {
+                        int32_t* d_status, const pzk_exec* exec, hipStream_t dep = nullptr,
+                        const uint8_t* d_packed = nullptr) {
   const int set = (int)(I->calls % I->nsets);
   Scratch& S = I->scr[set];
   int rc = ensure_chain_streams(I);
   if (rc) return rc;
   rc = ensure_scratch(I, S, batch);
   if (rc) return rc;
+  if (d_packed) {
+    if ((rc = ensure_in_rows(I, &S, batch))) return rc;
+    d_inputs = S.d_in_rows;
+  }
   I->calls++;
   hipStream_t user = (exec && exec->stream) ? (hipStream_t)exec->stream : nullptr;
   // PZK_SERIAL=1 (profiling): every phase on the main stream, so kernel times are standalone
@@ -918,6 +960,9 @@ static int batch_locked(pzk_instance* I, const uint8_t* d_inputs, size_t batch, 
   }
   const uint32_t B = (uint32_t)batch;
   const Layout& lay = I->lay;
+  if (d_packed)
+    HIPCHK(launch_unpack_inputs(I->d_packed_groups, (uint32_t)I->packed.groups.size(), lay.n_inputs, I->packed.row_bytes,
+                                d_packed, S.d_in_rows, B, st));
   const uint32_t ect_split = I->ect_split;
   DevLayout L = I->dev_layout();
   ValueStore vs{S.d_values, B};
@@ -1234,8 +1279,9 @@ static int batch_locked(pzk_instance* I, const uint8_t* d_inputs, size_t batch, 
 // chunk's call waits for the main stream (batch_locked's dep), whichever stream its chain runs on. The caller's
 // stream is joined the same way (its inputs may still be in flight there).
 static constexpr size_t MAP_CHUNK = 1024, MAP_CHUNK_MIN = 64;  // witnesses per O0 chunk (halved while it does not fit)
+// Packed inputs (d_packed, d_inputs null): each chunk's call expands its own rows, row_bytes per witness.
 static int batch_mapped(pzk_instance* I, const uint8_t* d_inputs, size_t batch, uint8_t* d_wtns, size_t stride,
-                        int32_t* d_status, const pzk_exec* exec) {
+                        int32_t* d_status, const pzk_exec* exec, const uint8_t* d_packed = nullptr) {
   const size_t o0_stride = 32ull * I->lay.wit_size;
   size_t chunk = std::min(batch, MAP_CHUNK);
   if (chunk > I->o0_cap) {  // the chains cost the same for any chunk size: take the largest that fits
@@ -1265,8 +1311,9 @@ static int batch_mapped(pzk_instance* I, const uint8_t* d_inputs, size_t batch, 
     const size_t n = std::min(chunk, batch - lo);
     const int set = (int)(I->calls % I->nsets), slot = (int)((lo / chunk) & 1);
     HIPCHK(hipStreamWaitEvent(I->stream, I->ev_gather[slot], 0));  // the gather two chunks back read this slot
-    int rc = batch_locked(I, d_inputs + 32ull * I->lay.n_inputs * lo, n, I->d_o0[slot], o0_stride,
-                          d_status ? d_status + lo : nullptr, &ex, I->stream);
+    int rc = batch_locked(I, d_packed ? nullptr : d_inputs + 32ull * I->lay.n_inputs * lo, n, I->d_o0[slot], o0_stride,
+                          d_status ? d_status + lo : nullptr, &ex, I->stream,
+                          d_packed ? d_packed + I->packed.row_bytes * lo : nullptr);
     if (rc) return rc;
     for (int i = 0; i < pzk_instance::NSTREAMS; i++) HIPCHK(hipStreamWaitEvent(I->stream, I->ev_done[set][i], 0));
     HIPCHK(launch_wtns_gather(I->d_o0[slot], o0_stride, I->d_map, I->out_size, d_wtns + stride * lo, stride, (uint32_t)n,
@@ -1284,9 +1331,11 @@ static int batch_mapped(pzk_instance* I, const uint8_t* d_inputs, size_t batch, 
   return 0;
 }
 
+// packed: d_inputs holds packed rows (pzk_witness_batch_packed)
 static int pzk_witness_batch_impl(pzk_instance* I, const uint8_t* d_inputs, size_t batch, uint8_t* d_wtns, size_t stride,
-                      int32_t* d_status, const pzk_exec* exec) {
+                      int32_t* d_status, const pzk_exec* exec, bool packed = false) {
   if (!I || !d_inputs || !d_wtns) return fail(PZK_E_ARG, "null argument");
+  if (packed && (uintptr_t)d_inputs % 16) return fail(PZK_E_ARG, "packed rows must be 16-byte aligned");
   if (batch == 0) return 0;
   if (batch > 65535) return fail(PZK_E_ARG, "batch > 65535: split it");
   if (stride < 32ull * I->out_size || stride % 16) return fail(PZK_E_ARG, "bad witness stride");
@@ -1295,8 +1344,40 @@ static int pzk_witness_batch_impl(pzk_instance* I, const uint8_t* d_inputs, size
   std::lock_guard<std::mutex> lock(I->mu);
   DeviceGuard dg(I->device);
   if (dg.err != hipSuccess) return fail(PZK_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dg.err));
+  if (packed) {
+    if (I->d_map) return batch_mapped(I, nullptr, batch, d_wtns, stride, d_status, exec, d_inputs);
+    return batch_locked(I, nullptr, batch, d_wtns, stride, d_status, exec, nullptr, d_inputs);
+  }
   if (I->d_map) return batch_mapped(I, d_inputs, batch, d_wtns, stride, d_status, exec);
   return batch_locked(I, d_inputs, batch, d_wtns, stride, d_status, exec);  // O0, or a monotone map emitted directly
+}
+
+static int pzk_unpack_inputs_impl(pzk_instance* I, const uint8_t* d_packed, size_t batch, uint8_t* d_rows,
+                                  const pzk_exec* exec) {
+  if (!I || !d_packed || !d_rows) return fail(PZK_E_ARG, "null argument");
+  if (batch == 0) return 0;
+  if (batch > 65535) return fail(PZK_E_ARG, "batch > 65535: split it");
+  if ((uintptr_t)d_packed % 16 || (uintptr_t)d_rows % 16) return fail(PZK_E_ARG, "packed rows and rows must be 16-byte aligned");
+  int rc = check_exec_device(I, exec);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lock(I->mu);
+  DeviceGuard dg(I->device);
+  if (dg.err != hipSuccess) return fail(PZK_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(dg.err));
+  if ((rc = ensure_in_rows(I, nullptr, 0))) return rc;
+  hipStream_t st = (exec && exec->stream) ? (hipStream_t)exec->stream : I->stream;
+  HIPCHK(launch_unpack_inputs(I->d_packed_groups, (uint32_t)I->packed.groups.size(), I->lay.n_inputs, I->packed.row_bytes,
+                              d_packed, d_rows, (uint32_t)batch, st));
+  if (exec && (exec->flags & PZK_EXEC_SYNC)) HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+static int pzk_instance_input_packed_impl(const pzk_instance* I, uint32_t i, uint32_t* kind, uint64_t* off, uint64_t* len) {
+  if (!I || i >= I->packed.groups.size()) return fail(PZK_E_ARG, "input index out of range");
+  const PackedGroup& g = I->packed.groups[i];
+  if (kind) *kind = g.kind;
+  if (off) *off = g.byte_off;
+  if (len) *len = packed_group_bytes(g.kind, g.elem_len);
+  return 0;
 }
 
 static int pzk_instance_sync_impl(pzk_instance* I) {
@@ -1307,8 +1388,9 @@ static int pzk_instance_sync_impl(pzk_instance* I) {
   return sync_all(I);
 }
 
+// packed: h_inputs holds packed rows (pzk_witness_batch_host_packed); they go up into the same staging buffer
 static int pzk_witness_batch_host_impl(pzk_instance* I, const uint8_t* h_inputs, size_t batch, uint8_t* h_wtns,
-                           int32_t* h_status, const pzk_exec* exec) {
+                           int32_t* h_status, const pzk_exec* exec, bool packed = false) {
   if (!I || !h_inputs || !h_wtns) return fail(PZK_E_ARG, "null argument");
   if (batch == 0) return 0;
   if (batch > 65535) return fail(PZK_E_ARG, "batch > 65535: split it");
@@ -1331,11 +1413,12 @@ static int pzk_witness_batch_host_impl(pzk_instance* I, const uint8_t* h_inputs,
     I->host_cap = batch;
   }
   hipStream_t st = I->stream;
-  HIPCHK(hipMemcpyAsync(I->d_in, h_inputs, in_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(I->d_in, h_inputs, packed ? I->packed.row_bytes * batch : in_bytes, hipMemcpyHostToDevice, st));
   pzk_exec ex{I->device, exec ? (exec->flags & PZK_EXEC_TIMING) : 0, nullptr};
+  const uint8_t *d_full = packed ? nullptr : I->d_in, *d_pk = packed ? I->d_in : nullptr;
   // the upload is on the main stream: batch_mapped orders every chunk after it, batch_locked via dep
-  rc = I->d_map ? batch_mapped(I, I->d_in, batch, I->d_out, 32ull * I->out_size, I->d_status, &ex)
-                : batch_locked(I, I->d_in, batch, I->d_out, 32ull * I->out_size, I->d_status, &ex, st);
+  rc = I->d_map ? batch_mapped(I, d_full, batch, I->d_out, 32ull * I->out_size, I->d_status, &ex, d_pk)
+                : batch_locked(I, d_full, batch, I->d_out, 32ull * I->out_size, I->d_status, &ex, st, d_pk);
   if (rc) return rc;
   if ((rc = sync_all(I))) return rc;
   HIPCHK(hipMemcpy(h_wtns, I->d_out, out_bytes, hipMemcpyDeviceToHost));
@@ -1525,6 +1608,25 @@ int pzk_wtns_header(const pzk_instance* I, uint8_t h[76]) {
 int pzk_witness_batch(pzk_instance* I, const uint8_t* d_inputs, size_t batch, uint8_t* d_wtns, size_t stride,
                       int32_t* d_status, const pzk_exec* exec) {
   return guarded([&] { return pzk_witness_batch_impl(I, d_inputs, batch, d_wtns, stride, d_status, exec); });
+}
+
+int pzk_witness_batch_packed(pzk_instance* I, const uint8_t* d_packed, size_t batch, uint8_t* d_wtns, size_t stride,
+                             int32_t* d_status, const pzk_exec* exec) {
+  return guarded([&] { return pzk_witness_batch_impl(I, d_packed, batch, d_wtns, stride, d_status, exec, true); });
+}
+
+int pzk_witness_batch_host_packed(pzk_instance* I, const uint8_t* h_packed, size_t batch, uint8_t* h_wtns,
+                                  int32_t* h_status, const pzk_exec* exec) {
+  return guarded([&] { return pzk_witness_batch_host_impl(I, h_packed, batch, h_wtns, h_status, exec, true); });
+}
+
+int pzk_unpack_inputs(pzk_instance* I, const uint8_t* d_packed, size_t batch, uint8_t* d_rows, const pzk_exec* exec) {
+  return guarded([&] { return pzk_unpack_inputs_impl(I, d_packed, batch, d_rows, exec); });
+}
+
+int pzk_instance_input_packed(const pzk_instance* I, uint32_t i, uint32_t* kind, uint64_t* byte_offset,
+                              uint64_t* byte_length) {
+  return guarded([&] { return pzk_instance_input_packed_impl(I, i, kind, byte_offset, byte_length); });
 }
 
 int pzk_instance_sync(pzk_instance* I) {

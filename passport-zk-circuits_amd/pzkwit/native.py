@@ -16,12 +16,15 @@ LIB_PATH = os.environ.get("PZK_LIB") or os.path.join(PKG, "lib", "libpzkwit.so")
 PZK_CIRCUIT_REGISTER, PZK_CIRCUIT_POSEIDON, PZK_CIRCUIT_SHA256, PZK_CIRCUIT_SHA1 = 0, 1, 2, 3
 PZK_CIRCUIT_SHA384, PZK_CIRCUIT_SHA512, PZK_CIRCUIT_QUERY, PZK_CIRCUIT_LIGHT = 4, 5, 6, 7
 PZK_EXEC_SYNC = 1
+PZK_INPUT_BIT, PZK_INPUT_LIMB, PZK_INPUT_FIELD = 0, 1, 2  # packed input group kinds
 
 # C-ABI entry points declared in include/pzkwit.h and include/pzkpassport.h (checked by tests/test_capi.py)
 EXPORTS = ("pzk_instance_create", "pzk_instance_destroy", "pzk_instance_info", "pzk_instance_input",
            "pzk_wtns_header", "pzk_witness_batch", "pzk_witness_batch_host", "pzk_instance_sync",
            "pzk_instance_create_mapped", "pzk_sym_check", "pzk_timing", "pzk_phase_info", "pzk_last_error",
-           "pzk_version", "pzk_passport_parse", "pzk_passport_inputs")
+           "pzk_version", "pzk_passport_parse", "pzk_passport_inputs", "pzk_packed_layout", "pzk_packed_group",
+           "pzk_instance_input_packed", "pzk_pack_inputs", "pzk_unpack_inputs_host", "pzk_unpack_inputs",
+           "pzk_witness_batch_packed", "pzk_witness_batch_host_packed", "pzk_passport_inputs_packed")
 
 STATUS_NAMES = {
     0: "OK", 1: "Num2Bits (bitify.circom:26)", 2: "AliasCheck (aliascheck.circom:14)",
@@ -106,6 +109,19 @@ def lib():
                                        ctypes.POINTER(ctypes.c_uint32)]
         L.pzk_layout_region.argtypes = [ctypes.POINTER(PzkParams), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64),
                                         ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+        L.pzk_packed_layout.argtypes = [ctypes.POINTER(PzkParams), ctypes.POINTER(ctypes.c_uint64)]
+        L.pzk_packed_group.argtypes = [ctypes.POINTER(PzkParams), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                       ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        L.pzk_instance_input_packed.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+        L.pzk_pack_inputs.argtypes = [ctypes.POINTER(PzkParams), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_int]
+        L.pzk_unpack_inputs_host.argtypes = [ctypes.POINTER(PzkParams), ctypes.c_void_p, ctypes.c_size_t,
+                                             ctypes.c_void_p]
+        L.pzk_unpack_inputs.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                        ctypes.POINTER(PzkExec)]
+        L.pzk_witness_batch_packed.argtypes = L.pzk_witness_batch.argtypes
+        L.pzk_witness_batch_host_packed.argtypes = L.pzk_witness_batch_host.argtypes
         L.pzk_last_error.restype = ctypes.c_char_p
         L.pzk_version.restype = ctypes.c_char_p
         _lib = L
@@ -130,6 +146,65 @@ def layout_witness_size(params, circuit=None):
 def layout_inputs(params, circuit=None):
     """Input elements (flat row length / 32) of a RegisterIdentityBuilder instance (no device)."""
     return int(layout_info(params, circuit).n_inputs)
+
+
+def _params(params, circuit=None, size_arg=0):
+    p = PzkParams(circuit=PZK_CIRCUIT_REGISTER if circuit is None else circuit, size_arg=size_arg)
+    for k, v in param_fields(params or {}).items():
+        setattr(p, k, v)
+    return p
+
+
+def packed_layout(params=None, circuit=None, size_arg=0):
+    """The packed input row of an instance (host only) -> (row_bytes, [(kind, byte offset, byte
+    length)]), one entry per input group in flat-input order (Instance.input_groups)."""
+    p = _params(params, circuit, size_arg)
+    info = PzkInfo()
+    _check(lib().pzk_layout_query(ctypes.byref(p), ctypes.byref(info), None))
+    rb = ctypes.c_uint64()
+    _check(lib().pzk_packed_layout(ctypes.byref(p), ctypes.byref(rb)))
+    groups = []
+    for i in range(info.n_input_groups):
+        kd, off, ln = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().pzk_packed_group(ctypes.byref(p), i, ctypes.byref(kd), ctypes.byref(off), ctypes.byref(ln)))
+        groups.append((int(kd.value), int(off.value), int(ln.value)))
+    return int(rb.value), groups
+
+
+def pack_inputs(rows, params=None, circuit=None, size_arg=0, threads=0):
+    """Full rows (n, n_inputs, 32) uint8 -> (packed (n, row_bytes) uint8, status (n,) int32): status 1 = the row has
+    no packed form (a non-bit in a BIT group, a limb >= 2^64), its packed row is zero; keep it on the unpacked path."""
+    p = _params(params, circuit, size_arg)
+    info = PzkInfo()
+    _check(lib().pzk_layout_query(ctypes.byref(p), ctypes.byref(info), None))
+    a = np.ascontiguousarray(rows, dtype=np.uint8)
+    if a.ndim == 2:
+        a = a[None]
+    assert a.shape[1:] == (int(info.n_inputs), 32), a.shape
+    rb = ctypes.c_uint64()
+    _check(lib().pzk_packed_layout(ctypes.byref(p), ctypes.byref(rb)))
+    out = np.empty((a.shape[0], int(rb.value)), dtype=np.uint8)
+    st = np.zeros(a.shape[0], dtype=np.int32)
+    _check(lib().pzk_pack_inputs(ctypes.byref(p), a.ctypes.data, a.shape[0], out.ctypes.data, st.ctypes.data,
+                                 int(threads)))
+    return out, st
+
+
+def unpack_inputs_host(packed, params=None, circuit=None, size_arg=0):
+    """Packed rows (n, row_bytes) uint8 -> full rows (n, n_inputs, 32) uint8, on the host (the GPU kernel's
+    reference)."""
+    p = _params(params, circuit, size_arg)
+    info = PzkInfo()
+    _check(lib().pzk_layout_query(ctypes.byref(p), ctypes.byref(info), None))
+    rb = ctypes.c_uint64()
+    _check(lib().pzk_packed_layout(ctypes.byref(p), ctypes.byref(rb)))
+    a = np.ascontiguousarray(packed, dtype=np.uint8)
+    if a.ndim == 1:
+        a = a[None]
+    assert a.shape[1:] == (int(rb.value),), a.shape
+    out = np.empty((a.shape[0], int(info.n_inputs), 32), dtype=np.uint8)
+    _check(lib().pzk_unpack_inputs_host(ctypes.byref(p), a.ctypes.data, a.shape[0], out.ctypes.data))
+    return out
 
 
 def sym_check(params, sym, circuit=None, size_arg=0):
@@ -175,11 +250,20 @@ class Instance:
         self.n_inputs = int(info.n_inputs)
         self.n_outputs = int(info.n_outputs)
         self.n_public_inputs = int(info.n_public_inputs)
+        self.pipeline_depth = int(info.pipeline_depth)
         self.input_groups = []
         for i in range(info.n_input_groups):
             nm, off, ln = ctypes.c_char_p(), ctypes.c_uint64(), ctypes.c_uint64()
             _check(L.pzk_instance_input(h, i, ctypes.byref(nm), ctypes.byref(off), ctypes.byref(ln)))
             self.input_groups.append((nm.value.decode(), int(off.value), int(ln.value)))
+        # the packed input row: per group (kind, byte offset, byte length); bytes per row
+        self.packed_groups = []
+        for i in range(info.n_input_groups):
+            kd, off, ln = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+            _check(L.pzk_instance_input_packed(h, i, ctypes.byref(kd), ctypes.byref(off), ctypes.byref(ln)))
+            self.packed_groups.append((int(kd.value), int(off.value), int(ln.value)))
+        end = max(o + n for _, o, n in self.packed_groups)
+        self.packed_row_bytes = (end + 15) & ~15
 
     def close(self):
         if getattr(self, "_h", None):
@@ -204,6 +288,20 @@ class Instance:
         ex = PzkExec(device=device, flags=(PZK_EXEC_SYNC if sync else 0) | (2 if timing else 0), stream=stream)
         _check(lib().pzk_witness_batch(self._h, ctypes.c_void_p(d_inputs), batch, ctypes.c_void_p(d_wtns), stride,
                                        ctypes.c_void_p(d_status) if d_status else None, ctypes.byref(ex)))
+
+    def unpack_inputs_device(self, d_packed, batch, d_rows, stream=None, device=-1, sync=True):
+        """Device packed rows -> caller-owned device full rows (pzk_unpack_inputs; both 16-byte aligned).
+        stream=None: the instance's main stream; synchronise before a call reads the rows."""
+        ex = PzkExec(device=device, flags=PZK_EXEC_SYNC if sync else 0, stream=stream)
+        _check(lib().pzk_unpack_inputs(self._h, ctypes.c_void_p(d_packed), batch, ctypes.c_void_p(d_rows),
+                                       ctypes.byref(ex)))
+
+    def witness_batch_packed_device(self, d_packed, batch, d_wtns, stride, d_status=None, stream=None, device=-1,
+                                    sync=False, timing=False):
+        """witness_batch_device on packed rows (pzk_witness_batch_packed): d_packed = batch x packed_row_bytes."""
+        ex = PzkExec(device=device, flags=(PZK_EXEC_SYNC if sync else 0) | (2 if timing else 0), stream=stream)
+        _check(lib().pzk_witness_batch_packed(self._h, ctypes.c_void_p(d_packed), batch, ctypes.c_void_p(d_wtns), stride,
+                                              ctypes.c_void_p(d_status) if d_status else None, ctypes.byref(ex)))
 
     def sync(self):
         """Wait for every call issued on this instance (pzk_instance_sync)."""
@@ -264,4 +362,18 @@ class Instance:
         ex = PzkExec(device=-1, flags=0, stream=None)
         _check(lib().pzk_witness_batch_host(self._h, a.ctypes.data, b, out.ctypes.data, st.ctypes.data,
                                             ctypes.byref(ex)))
+        return out, st
+
+    def witness_batch_host_packed(self, packed):
+        """packed: (batch, packed_row_bytes) uint8 -> (witness (batch, W, 32) uint8, status (batch,) int32)."""
+        a = np.ascontiguousarray(packed, dtype=np.uint8)
+        if a.ndim == 1:
+            a = a[None]
+        b = a.shape[0]
+        assert a.shape[1:] == (self.packed_row_bytes,), a.shape
+        out = np.empty((b, self.witness_size, 32), dtype=np.uint8)
+        st = np.zeros(b, dtype=np.int32)
+        ex = PzkExec(device=-1, flags=0, stream=None)
+        _check(lib().pzk_witness_batch_host_packed(self._h, a.ctypes.data, b, out.ctypes.data, st.ctypes.data,
+                                                   ctypes.byref(ex)))
         return out, st

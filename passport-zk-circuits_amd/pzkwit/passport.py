@@ -32,6 +32,7 @@ def _lib():
         L.pzk_passport_parse.argtypes = [ctypes.POINTER(PassportSrc), ctypes.POINTER(PassportInfo)]
         L.pzk_passport_inputs.argtypes = [ctypes.POINTER(native.PzkParams), ctypes.POINTER(PassportSrc), ctypes.c_size_t,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.pzk_passport_inputs_packed.argtypes = L.pzk_passport_inputs.argtypes
         L._pp_ready = True
     return L
 
@@ -108,6 +109,29 @@ def input_rows(params, passports, identity=None, threads=0, out=None):
     native._check(_lib().pzk_passport_inputs(ctypes.byref(p), src.arr, n,
                                              ident.ctypes.data if ident is not None else None,
                                              rows.ctypes.data, status.ctypes.data, int(threads)))
+    return rows, status
+
+
+def packed_rows(params, passports, identity=None, threads=0, out=None):
+    """input_rows with the rows written packed (pzk_passport_inputs_packed): -> (rows (n, row_bytes)
+    uint8 for Instance.witness_batch_host_packed / witness_batch_packed_device, status (n,) int32)."""
+    p = native.PzkParams(circuit=native.PZK_CIRCUIT_REGISTER)
+    for k, v in native.param_fields(params).items():
+        setattr(p, k, v)
+    rb = ctypes.c_uint64()
+    native._check(native.lib().pzk_packed_layout(ctypes.byref(p), ctypes.byref(rb)))
+    n = len(passports)
+    rows = out if out is not None else np.zeros((n, int(rb.value)), dtype=np.uint8)
+    assert rows.shape == (n, int(rb.value)) and rows.dtype == np.uint8 and rows.flags.c_contiguous
+    status = np.zeros(n, dtype=np.int32)
+    ident = None
+    if identity is not None:
+        ident = np.ascontiguousarray(identity, dtype=np.uint8)
+        assert ident.shape == (n, 82, 32), ident.shape
+    src = sources(passports)
+    native._check(_lib().pzk_passport_inputs_packed(ctypes.byref(p), src.arr, n,
+                                                    ident.ctypes.data if ident is not None else None,
+                                                    rows.ctypes.data, status.ctypes.data, int(threads)))
     return rows, status
 
 

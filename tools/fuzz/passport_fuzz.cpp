@@ -11,6 +11,8 @@ namespace pzk {
 int api_fail(int code, const std::string&) { return code; }
 }
 extern "C" int pzk_layout_query(const pzk_params*, pzk_info*, uint32_t*) { return PZK_E_PARAMS; }
+extern "C" int pzk_packed_layout(const pzk_params*, uint64_t*) { return PZK_E_PARAMS; }
+extern "C" int pzk_packed_group(const pzk_params*, uint32_t, uint32_t*, uint64_t*, uint64_t*) { return PZK_E_PARAMS; }
 
 static bool read_blob(std::vector<uint8_t>& v) {
   uint32_t n;
