@@ -145,6 +145,36 @@ def test_register_failing_checks_flag_lanes(oracle, gen):
     assert codes[3] in (8, 9, 10) and st[3] in (8, 9, 10)
 
 
+def _rsa_rows(gen, first, pairs, K=32):
+    """One unmodified row, then one row per (modulus, signature) pair (None keeps the passport's own value)."""
+    pps = [gen.passport_at(first + i) for i in range(len(pairs) + 1)]
+    rows = np.stack([I.pack_register_inputs(p) for p in pps])
+    ecL = I.CANONICAL["ec_blocks"] * 512
+    sig0 = 1 + ecL + 1024 + I.CANONICAL["dg15_blocks"] * 512 + 1024
+    for b, pair in enumerate(pairs, start=1):
+        for at, value in zip((sig0 + K, sig0), pair):
+            if value is None:
+                continue
+            assert 0 <= value < 1 << (64 * K)
+            rows[b, at:at + K] = 0
+            rows[b, at:at + K, :8] = np.frombuffer(value.to_bytes(8 * K, "little"), dtype=np.uint8).reshape(K, 8)
+    return rows
+
+
+def _check_rsa_rows(oracle, rows):
+    """Row 0 passes bit-exact with status 0; the others fail the EM checks in the oracle and on the GPU alike, and every
+    witness element still equals the oracle's."""
+    inst = native.Instance(native.PZK_CIRCUIT_REGISTER, 0, I.CANONICAL)
+    wit, st = inst.witness_batch_host(rows)
+    prm = oracle.register_params(**I.CANONICAL)
+    regions = region_table(I.CANONICAL)
+    for b in range(rows.shape[0]):
+        rc, ref = oracle.register_witness(prm, rows[b])
+        assert (rc == 0) == (b == 0) and (st[b] == 0) == (b == 0), (b, rc, st[b])
+        rep = mismatch_report(ref, wit[b], regions)
+        assert not rep, "row %d: %s" % (b, rep)
+
+
 def test_register_rsa_outside_barrett_domain_matches_oracle(oracle, gen):
     """The cooperative RSA core (rsa_coop.hpp) uses Barrett reduction only when x*y < b^(2k), k the
     modulus' significant limbs, and exact Knuth D otherwise. A 31-limb modulus (top limb zero) with a
@@ -162,15 +192,41 @@ def test_register_rsa_outside_barrett_domain_matches_oracle(oracle, gen):
         rows[b, pk0 + K - 1] = 0
         rows[b, sig0 + K - 1] = 0
         rows[b, sig0 + K - 1, 0] = 0x39 * b  # x = sig: x^2 >= b^62 = b^(2k) -> outside Barrett's domain
-    inst = native.Instance(native.PZK_CIRCUIT_REGISTER, 0, I.CANONICAL)
-    wit, st = inst.witness_batch_host(rows)
-    prm = oracle.register_params(**I.CANONICAL)
-    regions = region_table(I.CANONICAL)
-    for b in range(3):
-        rc, ref = oracle.register_witness(prm, rows[b])
-        assert (rc == 0) == (b == 0) and (st[b] == 0) == (b == 0), (b, rc, st[b])
-        rep = mismatch_report(ref, wit[b], regions)
-        assert not rep, "row %d: %s" % (b, rep)
+    _check_rsa_rows(oracle, rows)
+
+
+def test_register_rsa_barrett_corrections_match_oracle(oracle, gen):
+    """k_rsa_core2's Barrett correction count (corr = 1 and 2, then the + corr * n_i fix-up of the column sums that
+    feed the BigIntIsZero carries) on multiplication 0, at 32 and at 31 significant limbs. Real keys have a normalised
+    top limb and never need two corrections; a modulus with a top limb of 1..5 and a signature near b^k does. The
+    pairs come from a seeded search over the model of the estimate (arith_cases.barrett_search)."""
+    import arith_cases as A
+    pairs = []
+    for limbs in (32, 31):
+        found = A.barrett_search(limbs)
+        for corr in (1, 2):
+            assert found[corr], "no corr = %d pair at %d limbs in %d tries" % (corr, limbs, A.BARRETT_TRIES)
+            n, sig = found[corr][0]
+            assert A.model_barrett(n, sig, sig) == corr
+            pairs.append((n, sig))
+    _check_rsa_rows(oracle, _rsa_rows(gen, 400, pairs))
+
+
+def test_register_rsa_extreme_moduli_match_oracle(oracle, gen):
+    """Operands at the ends of k_rsa_core2's ranges: signature = modulus = b^K - 1; modulus b^(K-1) (top limb 1, the
+    rest zero: mu = b^(K+1) fills its last word); every limb all ones under a top limb of 2^63; and a Knuth D row
+    (signature >= modulus, 31 significant limbs: multiplication 0 is outside the Barrett domain) whose division
+    reaches add-back by the model."""
+    import arith_cases as A
+    K = 32
+    top = 1 << (64 * K)
+    addback = A.rsa_knuth_addback_row()
+    assert addback is not None
+    n, sig = addback
+    assert "addback" in A.model_knuth_d(sig * sig, 2 * K, n, K - 1)[2]
+    pairs = [(top - 1, top - 1), (1 << (64 * (K - 1)), None), ((1 << (64 * K - 1)) | ((1 << (64 * (K - 1))) - 1), None),
+             addback]
+    _check_rsa_rows(oracle, _rsa_rows(gen, 410, pairs))
 
 
 @pytest.mark.parametrize("params", [dict(I.CANONICAL, sig=3, dg_hash=160), dict(I.CANONICAL, sig=1, dg_hash=160, aa=0),
