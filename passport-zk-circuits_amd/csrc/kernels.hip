@@ -110,27 +110,45 @@ __global__ void __launch_bounds__(EMIT_THREADS) k_emit_sha(DevLayout L, const Wo
     }
     __syncthreads();
     // stage 2: one descriptor, one LDS word, one bit-field extract per element
-    // Two lanes per element (16 B each), so every wave store is 1 KiB contiguous: the element
-    // is cheap enough to evaluate twice, and this store shape writes ~19 % faster than 32 B per
-    // lane (emit_run stages through LDS for the emitters whose elements are expensive).
-    // SHA_U descriptors are loaded before the SHA_U stores that use them (a global load issued
+    // Two lanes per element (16 B each) STORE, so every wave store is 1 KiB contiguous (this store
+    // shape writes ~19 % faster than 32 B per lane), but each element is evaluated once: a wave
+    // takes groups of 64 consecutive elements, lane l evaluates element g0 + l, and the group's
+    // two wave stores fetch their values across the lanes (store_pair, mapsink.hpp; emit_run
+    // stages through LDS for the emitters whose elements are expensive). The exchange runs with
+    // all 64 lanes active: the loop and the full / tail choice are workgroup-uniform, lanes past
+    // the run take part with descriptor 0, and only the tail's stores are predicated.
+    // SHA_U / 2 descriptors are loaded before the SHA_U stores that use them (a global load issued
     // after a store waits for it: gfx9 vmcnt counts both)
     // Mapped: the kept elements' descriptors (desc_run), stored consecutively from their mapped index.
     const DescRun dr = desc_run<MM>(L, wtns, stride, w, wk, R.off + wk.start, L.sha_prog + wk.start);
     const uint32_t* prog = dr.prog;
-    const uint32_t tot = 2 * dr.count;
-    for (uint32_t base = threadIdx.x; base < tot; base += SHA_U * blockDim.x) {
-      uint32_t d[SHA_U];
+    const uint32_t count = dr.count;
+    constexpr int SHA_G = SHA_U / 2;  // groups per wave and iteration
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x - lane);
+    const uint32_t* pl = prog + lane;  // per-lane bases: a group's addresses are these plus a wave-uniform offset
+    uint4* dst = reinterpret_cast<uint4*>(dr.out.row + 32ull * dr.out.g);
+    for (uint32_t it = 0; it < count; it += SHA_G * blockDim.x) {
+      const uint32_t g0 = it + wave0;  // the wave's first group; group j starts at g0 + j * blockDim.x
+      uint32_t d[SHA_G];
+      if (it + SHA_G * blockDim.x <= count) {  // every group of the iteration lies inside the run
 #pragma unroll
-      for (int k = 0; k < SHA_U; k++) {
-        const uint32_t h = base + k * blockDim.x;
-        d[k] = h < tot ? prog[h >> 1] : 0u;
-      }
+        for (int j = 0; j < SHA_G; j++) d[j] = pl[g0 + j * blockDim.x];
 #pragma unroll
-      for (int k = 0; k < SHA_U; k++) {
-        const uint32_t h = base + k * blockDim.x;
-        const uint64_t v = (h & 1) ? 0 : sha_desc_apply(d[k], wt[d[k] & 2047]);
-        store_half<MAP_O0>(dr.out, h, make_uint4((uint32_t)v, (uint32_t)(v >> 32), 0u, 0u), h < tot);
+        for (int j = 0; j < SHA_G; j++)
+          store_pair<false>(dst + 2ull * (g0 + j * blockDim.x), 0, sha_desc_apply(d[j], wt[d[j] & 2047]));
+      } else {
+#pragma unroll
+        for (int j = 0; j < SHA_G; j++) {
+          const uint32_t q0 = g0 + j * blockDim.x;
+          d[j] = q0 + lane < count ? pl[q0] : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < SHA_G; j++) {
+          const uint32_t q0 = g0 + j * blockDim.x;
+          if (q0 >= count) break;  // wave-uniform
+          store_pair<true>(dst + 2ull * q0, 2 * (count - q0), sha_desc_apply(d[j], wt[d[j] & 2047]));
+        }
       }
     }
   } else {  // RK_SHA_OWN: H_0..H_B (H_m = Hin of block m, H_B = Hout)
@@ -475,10 +493,12 @@ hipError_t launch_emit(int emitter, const DevLayout& L, const Work* work, uint32
     case E_GEN: case E_GENR: hipLaunchKernelGGL(k_emit_gen, g, blk, 0, st, L, work, B); break;
     case E_QRY: hipLaunchKernelGGL(k_emit_qry, g, blk, 0, st, L, work, B); break;
     case E_SHA: case E_SHAD:  // witness-major grid (see k_emit_sha)
-    {  // PZK_SHA_U (8 / 16 / 32): prefetch depth, for tuning runs
-      static const int u = getenv("PZK_SHA_U") ? atoi(getenv("PZK_SHA_U")) : 16;
+    {  // PZK_SHA_U (8 / 16 / 32): stores in flight per wave and iteration, for tuning runs. O0 default 32: with one
+       // evaluation per element that is the 16 descriptor loads per iteration the loop had before, and beside the
+       // other emitters the default line runs +3.4 % over 16, +1.6 % over the earlier loop (profiles/r7a_ab/, table 2)
+      static const int u = getenv("PZK_SHA_U") ? atoi(getenv("PZK_SHA_U")) : 32;
       auto kern = L.keep.bits ? k_emit_sha<16, MAP_DIRECT>
-                  : u == 8 ? k_emit_sha<8, MAP_O0> : u == 32 ? k_emit_sha<32, MAP_O0> : k_emit_sha<16, MAP_O0>;
+                  : u == 8 ? k_emit_sha<8, MAP_O0> : u == 16 ? k_emit_sha<16, MAP_O0> : k_emit_sha<32, MAP_O0>;
       hipLaunchKernelGGL(kern, dim3(batch, n_work), blk, 0, st, L, work, B.inputs, B.derived, B.sha_core, B.wtns,
                          B.stride, 1);
       break;

@@ -85,6 +85,27 @@ __device__ __forceinline__ void store_half(const OutRow& o, uint32_t h, const ui
   if (valid && map_keep(m, e)) reinterpret_cast<uint4*>(o.row)[2ull * map_rank(m, e) + (h & 1)] = v;
 }
 
+// The same store shape for a group of 64 consecutive elements whose values are u64 and were evaluated once, lane l
+// holding element l of the group: the group's two wave stores, from half 0 of the group at dst (identity store, as
+// DescRun gives it). In store s lane l writes half l & 1 of element 32 s + (l >> 1): the even lanes the value they
+// fetch from that element's lane (ds_bpermute: no LDS allocation), the odd lanes zeros, the upper 16 B of a u64
+// element. A cross-lane read of an inactive lane returns 0, so this is called with all 64 lanes of the wave active,
+// outside every divergent branch; lanes past the run pass any value. TAIL: only the group's halves below n_half are
+// stored (without it no store is predicated).
+template <bool TAIL>
+__device__ __forceinline__ void store_pair(uint4* dst, uint32_t n_half, uint64_t v) {
+  const uint32_t lane = threadIdx.x & 63;
+  const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
+#pragma unroll
+  for (uint32_t s = 0; s < 2; s++) {
+    const int src = (int)(4u * (32u * s + (lane >> 1)));  // byte address of the source lane's dword
+    const uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute(src, lo);
+    const uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute(src, hi);
+    const uint4 e = (lane & 1) ? make_uint4(0u, 0u, 0u, 0u) : make_uint4(a, b, 0u, 0u);
+    if (!TAIL || 64u * s + lane < n_half) dst[64u * s + lane] = e;
+  }
+}
+
 // kept signals below O0 index g (wave-uniform g): the mapped row index of the first kept element at or after g
 __device__ __forceinline__ uint32_t map_rank_at(const KeepMap& M, uint64_t g) {
   const uint32_t i = __builtin_amdgcn_readfirstlane((uint32_t)(g >> 6));
