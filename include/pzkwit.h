@@ -245,6 +245,51 @@ typedef int (*pzk_sink_fn)(void* user, size_t first, size_t n, const uint8_t* ro
 int pzk_witness_stream(pzk_instance* inst, const uint8_t* h_inputs, size_t batch, size_t chunk, pzk_sink_fn sink,
                        void* user, const pzk_exec* exec);
 
+/* ---- Checking witness rows against a circom .r1cs file ----
+ * Replaces: circuit.checkConstraints(w) (test/automatisationTest.js:51), for a whole batch of rows resident in HBM.
+ * The file is circom's / snarkjs' binary format, version 1, over BN254's scalar field: a header section (type 1), a
+ * constraint section (type 2), optionally a wire-to-label section (type 3); sections in any order, other types
+ * skipped. Within a linear combination wires may come in any order and more than once (their coefficients add), and
+ * a coefficient may be 0. Rejected with PZK_E_ARG: wrong magic, version != 1, fieldSize != 32, another prime, a
+ * missing or duplicate type-1 or type-2 section, any size that runs past the buffer or its section, trailing bytes
+ * in the constraint section, a wire id >= nWires, a coefficient >= p, nWires = 0, a type-3 section that is not
+ * 8 * nWires bytes, mConstraints >= 2^31 (a constraint index fits the int32 result). */
+typedef struct pzk_r1cs pzk_r1cs;
+typedef struct pzk_r1cs_info {
+  uint32_t n_wires, n_pub_out, n_pub_in, n_prv_in;
+  uint64_t n_labels;
+  uint32_t n_constraints, n_long; /* n_long: constraints on the wave-per-constraint path (an LC of more than 32 terms) */
+  uint64_t n_terms;               /* after merging duplicate wires and dropping zero coefficients */
+  uint32_t n_coeffs, max_terms;   /* entries of the coefficient table: the distinct coefficients in use and the two
+                                     fixed entries 1 and p - 1; terms of the longest LC */
+} pzk_r1cs_info;
+
+/* Host only (no device needed); the program is uploaded at the object's first check. */
+int pzk_r1cs_load(const uint8_t* bytes, size_t len, pzk_r1cs** out);
+void pzk_r1cs_destroy(pzk_r1cs* r);
+int pzk_r1cs_get_info(const pzk_r1cs* r, pzk_r1cs_info* info);
+
+/* Check batch rows against the system on the GPU.
+ *   d_wtns         : batch rows of stride bytes (>= 32 * n_wires, a multiple of 16; device pointer 16-byte aligned),
+ *                    32 B little-endian per wire, as pzk_witness_batch writes them. An element >= p counts as its
+ *                    residue. Bytes past 32 * n_wires of a row are not read.
+ *   d_first_failed : batch x int32: -1 = every constraint holds, k >= 0 = the lowest index (file order) of a violated
+ *                    constraint
+ *   d_n_failed     : batch x uint32 violated constraints per row; may be NULL
+ * exec->stream: the check is ordered after it and runs on it. NULL: the object's own stream (the caller has
+ * synchronised whatever wrote the rows; complete after PZK_EXEC_SYNC or a device-wide synchronise). The object is
+ * bound to the device of its first check (exec->device, or < 0 / exec NULL: the current device); calls on one object
+ * are serialised by an internal mutex. batch = 0 returns 0. Without a device: PZK_E_NODEVICE. */
+int pzk_r1cs_check_batch(pzk_r1cs* r, const uint8_t* d_wtns, size_t batch, size_t stride, int32_t* d_first_failed,
+                         uint32_t* d_n_failed, const pzk_exec* exec);
+/* The same on host buffers (copies in and out; complete on return). */
+int pzk_r1cs_check_batch_host(pzk_r1cs* r, const uint8_t* h_wtns, size_t batch, size_t stride, int32_t* first_failed,
+                              uint32_t* n_failed, const pzk_exec* exec);
+/* The kernels' host twin, as pzk_unpack_inputs_host is k_unpack_inputs': plain C++, one thread, no device, same
+ * results. Not a fallback: the two entry points above never call it. */
+int pzk_r1cs_eval_host(const pzk_r1cs* r, const uint8_t* h_wtns, size_t batch, size_t stride, int32_t* first_failed,
+                       uint32_t* n_failed);
+
 /* Per-phase kernel time accumulated (ms) by calls made with PZK_EXEC_TIMING, and the number of
  * launches of each phase. On input *count is the capacity of the arrays; on output the number of
  * phases. Synchronises on the recorded events. reset != 0 clears the accumulators afterwards. */

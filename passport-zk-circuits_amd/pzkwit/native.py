@@ -24,7 +24,9 @@ EXPORTS = ("pzk_instance_create", "pzk_instance_destroy", "pzk_instance_info", "
            "pzk_instance_create_mapped", "pzk_sym_check", "pzk_timing", "pzk_phase_info", "pzk_last_error",
            "pzk_version", "pzk_passport_parse", "pzk_passport_inputs", "pzk_packed_layout", "pzk_packed_group",
            "pzk_instance_input_packed", "pzk_pack_inputs", "pzk_unpack_inputs_host", "pzk_unpack_inputs",
-           "pzk_witness_batch_packed", "pzk_witness_batch_host_packed", "pzk_passport_inputs_packed")
+           "pzk_witness_batch_packed", "pzk_witness_batch_host_packed", "pzk_passport_inputs_packed",
+           "pzk_r1cs_load", "pzk_r1cs_destroy", "pzk_r1cs_get_info", "pzk_r1cs_check_batch",
+           "pzk_r1cs_check_batch_host", "pzk_r1cs_eval_host")
 
 STATUS_NAMES = {
     0: "OK", 1: "Num2Bits (bitify.circom:26)", 2: "AliasCheck (aliascheck.circom:14)",
@@ -50,6 +52,13 @@ class PzkInfo(ctypes.Structure):
     _fields_ = [("witness_size", ctypes.c_uint64), ("n_inputs", ctypes.c_uint64), ("n_outputs", ctypes.c_uint32),
                 ("n_public_inputs", ctypes.c_uint32), ("n_input_groups", ctypes.c_uint32),
                 ("pipeline_depth", ctypes.c_uint32)]
+
+
+class PzkR1csInfo(ctypes.Structure):
+    _fields_ = [("n_wires", ctypes.c_uint32), ("n_pub_out", ctypes.c_uint32), ("n_pub_in", ctypes.c_uint32),
+                ("n_prv_in", ctypes.c_uint32), ("n_labels", ctypes.c_uint64), ("n_constraints", ctypes.c_uint32),
+                ("n_long", ctypes.c_uint32), ("n_terms", ctypes.c_uint64), ("n_coeffs", ctypes.c_uint32),
+                ("max_terms", ctypes.c_uint32)]
 
 
 class PzkExec(ctypes.Structure):
@@ -122,6 +131,15 @@ def lib():
                                         ctypes.POINTER(PzkExec)]
         L.pzk_witness_batch_packed.argtypes = L.pzk_witness_batch.argtypes
         L.pzk_witness_batch_host_packed.argtypes = L.pzk_witness_batch_host.argtypes
+        L.pzk_r1cs_load.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p)]
+        L.pzk_r1cs_destroy.argtypes = [ctypes.c_void_p]
+        L.pzk_r1cs_destroy.restype = None
+        L.pzk_r1cs_get_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(PzkR1csInfo)]
+        L.pzk_r1cs_check_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(PzkExec)]
+        L.pzk_r1cs_check_batch_host.argtypes = L.pzk_r1cs_check_batch.argtypes
+        L.pzk_r1cs_eval_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                         ctypes.c_void_p, ctypes.c_void_p]
         L.pzk_last_error.restype = ctypes.c_char_p
         L.pzk_version.restype = ctypes.c_char_p
         _lib = L
