@@ -762,15 +762,23 @@ __global__ void __launch_bounds__(64) k_ec_chain(DevLayout L, const uint8_t* inp
 }
 
 // Phase 1b, lane = witness: verifyECDSABits.add (the last op) of the two chains' results
-__global__ void __launch_bounds__(64) k_ec_final(uint64_t* ec_jac, uint32_t batch) {
+__global__ void __launch_bounds__(64) k_ec_final(DevLayout L, const uint8_t* inputs, uint64_t* ec_jac, uint32_t batch) {
   const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= batch) return;
+  const uint8_t* row = inputs + 32ull * (uint64_t)w * L.n_inputs;
   uint64_t* J = ec_jac + (size_t)w * ECG.jac_words;
   const int32_t* pts = reinterpret_cast<const int32_t*>(J + ECG.j_pts);
   const int h1 = pts[ec_pt_index(PT_GM_RP, ECG.parts - 2)], h2 = pts[ec_pt_index(PT_SM_RP, ECG.wins)];
-  // both are op outputs (a forwarded dummy would need an all-zero scalar, which fails BigModInv /
-  // the final check anyway): fall back to zero points otherwise
-  Jac P = h1 >= 0 ? jac_load(J + ECG.j_op * h1) : Jac{}, Q = h2 >= 0 ? jac_load(J + ECG.j_op * h2) : Jac{};
+  // A chain's result is an op output or a forwarded point (a negative handle), and a signature that verifies can
+  // give either: u1 with one non-zero byte forwards that byte's table entry, u2 = 1 forwards the key, and u2 = 0
+  // (r = 0 mod n, which fails only x1 mod n === r) forwards the dummy. All three are affine (Z = 1).
+  auto point = [&](int h) -> Jac {
+    if (h >= 0) return jac_load(J + ECG.j_op * h);
+    uint64_t xy[P2];
+    ec_aff_const(L, row, h, xy);
+    return jac_of_aff(xy);
+  };
+  const Jac P = point(h1), Q = point(h2);
   jac_store(J + ECG.j_op * ECG.op_final, jac_add(P, Q), h1, h2);
 }
 

@@ -21,7 +21,7 @@ hipError_t launch_ec_core_cv(const DevLayout& L, const uint8_t* inputs, const ui
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_ec_chain, dim3((2 * batch + 63) / 64), dim3(64), 0, st, L, inputs, ec_core, ec_jac, batch);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_ec_final, dim3((batch + 63) / 64), dim3(64), 0, st, ec_jac, batch);
+  hipLaunchKernelGGL(k_ec_final, dim3((batch + 63) / 64), dim3(64), 0, st, L, inputs, ec_jac, batch);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_ec_affine, dim3((batch * EC_AFF_GROUPS + 63) / 64), dim3(64), 0, st, ec_core, ec_jac, status,
                      batch);

@@ -31,7 +31,7 @@ def _run(oracle, params, rows, expect_ok=True):
     for b in range(rows.shape[0]):
         rc, ref = oracle.register_witness(prm, rows[b])
         codes.append(rc)
-        if rc == 0:
+        if rc in (0, 16):  # 16: only the last check (x1 mod n === r) fails, every element before it is defined
             rep = mismatch_report(ref, wit[b], regions)
             if rep:
                 reports.append("row %d: %s" % (b, rep))
