@@ -290,6 +290,47 @@ int pzk_r1cs_check_batch_host(pzk_r1cs* r, const uint8_t* h_wtns, size_t batch, 
 int pzk_r1cs_eval_host(const pzk_r1cs* r, const uint8_t* h_wtns, size_t batch, size_t stride, int32_t* first_failed,
                        uint32_t* n_failed);
 
+/* ---- Groth16's quotient evaluations for witness rows ----
+ * The first stage of `snarkjs groth16 prove` (circuits/scripts/prove.sh:25-27), for a batch of rows resident in HBM.
+ * With nC = n_constraints and nPub = n_pub_out + n_pub_in: M = nC + nPub + 1, N = 2^k the smallest power of two >= M
+ * (1 <= k <= 24, else PZK_E_ARG). Per row w: a_i = A_i.w and b_i = B_i.w for i < nC; a_(nC + s) = w_s, b_(nC + s) = 0
+ * for s = 0 .. nPub; zero from M on; c_i = a_i b_i. Each of a, b, c goes through an inverse transform of N points
+ * (factor 1 / N included), coefficient i times g^i, and a forward transform: its evaluations on the coset g <w_N>,
+ * where w_(2^28) = 5^((p - 1) / 2^28), w_(2^s) = w_(2^28)^(2^(28 - s)) and g = w_(2N). The result is
+ * h_j = a'_j b'_j - c'_j, j < N: natural order, 32 B little-endian, normal form, below p. On a row that violates the
+ * system h is still defined by the above, but it is not a quotient: check first. */
+typedef struct pzk_quotient_info {
+  uint32_t log2_n;        /* k */
+  uint32_t tile;          /* witnesses per tile of scratch */
+  uint64_t n, n_rows;     /* N, M */
+  uint64_t scratch_bytes; /* device memory the object takes at its first quotient call: the b and c vectors of a tile
+                             and the transforms' tables */
+} pzk_quotient_info;
+/* Host only. */
+int pzk_r1cs_quotient_info(const pzk_r1cs* r, pzk_quotient_info* info);
+
+/* h for batch rows, on the GPU.
+ *   d_wtns : as for pzk_r1cs_check_batch (an element >= p counts as its residue)
+ *   d_h    : batch rows of h_stride bytes (>= 32 * N, a multiple of 16; device pointer 16-byte aligned); bytes past
+ *            32 * N of a row are not written. The rows are the call's work memory too: they must not overlap d_wtns.
+ * Stream, device binding, the mutex, batch = 0 and PZK_E_NODEVICE as for pzk_r1cs_check_batch; on a caller stream
+ * nothing synchronises (the object's first quotient call allocates its scratch and builds its tables, and waits for
+ * that). Batches above pzk_quotient_info.tile run tile after tile on the same stream. With PZK_EXEC_TIMING the call
+ * synchronises after every tile and adds the time of its stages to pzk_r1cs_quotient_timing. */
+int pzk_r1cs_quotient_batch(pzk_r1cs* r, const uint8_t* d_wtns, size_t batch, size_t stride, uint8_t* d_h,
+                            size_t h_stride, const pzk_exec* exec);
+/* The same on host buffers (copies in and out; complete on return). */
+int pzk_r1cs_quotient_batch_host(pzk_r1cs* r, const uint8_t* h_wtns, size_t batch, size_t stride, uint8_t* h,
+                                 size_t h_stride, const pzk_exec* exec);
+/* The kernels' host twin: plain C++, one thread, no device, same bytes. Not a fallback: the two entry points above
+ * never call it. */
+int pzk_r1cs_quotient_host(const pzk_r1cs* r, const uint8_t* h_wtns, size_t batch, size_t stride, uint8_t* h,
+                           size_t h_stride);
+/* Milliseconds accumulated by quotient calls made with PZK_EXEC_TIMING: ms[0] the rows a, b, c; ms[1] the three
+ * inverse transforms (shift included); ms[2] the forward transforms of a and b; ms[3] the forward transform of c with
+ * the pointwise step folded into its last pass. reset != 0 clears them afterwards. */
+int pzk_r1cs_quotient_timing(pzk_r1cs* r, double ms[4], int reset);
+
 /* Per-phase kernel time accumulated (ms) by calls made with PZK_EXEC_TIMING, and the number of
  * launches of each phase. On input *count is the capacity of the arrays; on output the number of
  * phases. Synchronises on the recorded events. reset != 0 clears the accumulators afterwards. */

@@ -20,16 +20,7 @@ using namespace pzk;
 
 namespace {
 
-struct DevGuard {  // the caller's current device is restored on return (runtime.cpp DeviceGuard)
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DevGuard(int dev) {
-    err = hipGetDevice(&prev);
-    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
-    else prev = -1;
-  }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
+typedef R1csDevGuard DevGuard;
 
 void r1cs_dev_free(pzk_r1cs* r) {
   if (r->device < 0) return;
@@ -37,7 +28,8 @@ void r1cs_dev_free(pzk_r1cs* r) {
   if (dg.err != hipSuccess) return;
   R1csDevice& D = r->dev;
   if (D.stream) (void)hipStreamSynchronize(D.stream);
-  for (void* p : {(void*)D.lc_off, (void*)D.terms, (void*)D.coeffs, (void*)D.chunks, (void*)D.long_list})
+  for (void* p : {(void*)D.lc_off, (void*)D.terms, (void*)D.coeffs, (void*)D.chunks, (void*)D.long_list,
+                  (void*)D.quot_tables, (void*)D.quot_scratch})
     if (p) (void)hipFree(p);
   if (D.stream) (void)hipStreamDestroy(D.stream);
   D = R1csDevice();
@@ -54,8 +46,10 @@ int r1cs_upload(T** dst, const V* src, size_t n) {
   return 0;
 }
 
-// first check: the program goes to the current device, the coefficient table to Montgomery form there
-int r1cs_ensure_device(pzk_r1cs* r) {
+}  // namespace
+
+// first check (or quotient): the program goes to the current device, the coefficient table to Montgomery form there
+int pzk::r1cs_ensure_device(pzk_r1cs* r) {
   if (r->dev.stream) return 0;
   const R1csProgram& P = r->prog;
   R1csDevice& D = r->dev;
@@ -83,6 +77,8 @@ int r1cs_ensure_device(pzk_r1cs* r) {
   }
   return 0;
 }
+
+namespace {
 
 // both kernels on st; first_failed / n_failed are pre-set on the same stream
 int r1cs_launch(pzk_r1cs* r, const uint8_t* d_wtns, uint32_t batch, size_t stride, int32_t* d_first, uint32_t* d_n,
@@ -118,8 +114,10 @@ int r1cs_check_args(const pzk_r1cs* r, const void* wtns, size_t batch, size_t st
   return 0;
 }
 
+}  // namespace
+
 // device bound at the first check; the object's own stream unless the caller gives one
-int r1cs_bind(pzk_r1cs* r, const pzk_exec* ex) {
+int pzk::r1cs_bind(pzk_r1cs* r, const pzk_exec* ex) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
     (void)hipGetLastError();
@@ -136,6 +134,8 @@ int r1cs_bind(pzk_r1cs* r, const pzk_exec* ex) {
   }
   return 0;
 }
+
+namespace {
 
 int r1cs_check_batch_impl(pzk_r1cs* r, const uint8_t* d_wtns, size_t batch, size_t stride, int32_t* d_first,
                           uint32_t* d_n, const pzk_exec* ex) {

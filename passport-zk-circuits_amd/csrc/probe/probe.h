@@ -50,6 +50,16 @@ int pzk_probe_ec_field(int cv, int mod_n, int op, const uint32_t* a, const uint3
 // mp_divmod<PWORDS> by the curve's p (mod_n = 0) or n (1): a: n x 32 words, na[c] <= 31; q: n x 32, r: n x PWORDS
 int pzk_probe_ec_divmod(int cv, int mod_n, const uint64_t* a, const int* na, uint64_t* q, uint64_t* r, int n);
 
+// ---- the transforms of ntt.hpp: one forward or one inverse transform of batch x 2^k elements (8 words each, normal
+// form, below p; converted to and from Montgomery form around the transform). forward: coefficient i at index
+// bitrev_k(i) in, the evaluations at w_N^j in natural order out. inverse: evaluations in natural order in, coefficient
+// i at index bitrev_k(i) out, times g^i when shift != 0 (g = w_2N). split: n_split pass sizes q summing to k, each in
+// 1 .. r, or n_split = 0 for the default plan. on_device != 0: in and out are device pointers (they may be equal).
+int pzk_probe_ntt(int inverse, int shift, int k, int batch, const int* split, int n_split, const uint32_t* in,
+                  uint32_t* out, int on_device);
+// the default plan for 2^k points: returns the number of passes (0: k out of range), their sizes in q[0 .. 24), and r
+int pzk_probe_ntt_plan(int k, int* q, int* r);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@
 #include "../../include/pzkwit.h"
 #include "host_api.hpp"
 #include "r1cs.hpp"
+#define PZK_NTT_HOST_ONLY
+#include "ntt.hpp"
 
 namespace pzk {
 
@@ -93,6 +95,50 @@ F4 f_load(const uint8_t* p) {
   }
   return r;
 }
+
+void f_store(uint8_t* p, const F4& a) {
+  for (int i = 0; i < 4; i++)
+    for (int k = 0; k < 8; k++) p[8 * i + k] = (uint8_t)(a[i] >> (8 * k));
+}
+
+// ---- Montgomery form (R = 2^256) for the quotient's transforms: f_mul's bitwise reduction is too slow for them
+const F4 F_R2 = {0x1bb8e645ae216da7ull, 0x53fe3ab1e35c59e3ull, 0x8c49833d53bb8085ull, 0x0216d0b17f4e44a5ull};  // R^2 mod p
+const F4 F_ROOT28 = {0x9bd61b6e725b19f0ull, 0x402d111e41112ed4ull, 0x00e0a7eb8ef62abcull, 0x2a3c09f0a58a7e85ull};  // 5^((p - 1) / 2^28)
+uint64_t f_pinv() {  // -p^-1 mod 2^64, by Newton's iteration
+  uint64_t inv = 1;
+  for (int i = 0; i < 6; i++) inv *= 2 - FP[0] * inv;
+  return 0 - inv;
+}
+// a b / R mod p for a, b < p (operand-scanning CIOS; p < 2^254: the running sum stays below 2 p)
+F4 f_mmul(const F4& a, const F4& b) {
+  static const uint64_t pinv = f_pinv();
+  uint64_t t[6] = {0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < 4; i++) {
+    unsigned __int128 c = 0;
+    for (int j = 0; j < 4; j++) {
+      c += (unsigned __int128)a[j] * b[i] + t[j];
+      t[j] = (uint64_t)c;
+      c >>= 64;
+    }
+    c += t[4];
+    t[4] = (uint64_t)c;
+    t[5] = (uint64_t)(c >> 64);
+    const uint64_t m = t[0] * pinv;
+    c = ((unsigned __int128)m * FP[0] + t[0]) >> 64;
+    for (int j = 1; j < 4; j++) {
+      c += (unsigned __int128)m * FP[j] + t[j];
+      t[j - 1] = (uint64_t)c;
+      c >>= 64;
+    }
+    c += t[4];
+    t[3] = (uint64_t)c;
+    t[4] = t[5] + (uint64_t)(c >> 64);
+  }
+  F4 r = {t[0], t[1], t[2], t[3]};
+  if (t[4] || f_geq(r, FP)) f_sub_raw(r, FP);
+  return r;
+}
+F4 f_to_mont(const F4& a) { return f_mmul(a, F_R2); }
 
 // ---- bounded little-endian reader: nothing is read, and no size taken from the file is used, before it has been
 // compared with the bytes that remain
@@ -286,6 +332,104 @@ void r1cs_eval_row(const R1csProgram& P, const uint8_t* row, int32_t& first_fail
   }
 }
 
+bool r1cs_quotient_domain(const R1csProgram& P, uint64_t& m, int& k) {
+  m = (uint64_t)P.n_constraints + P.n_pub_out + P.n_pub_in + 1;
+  k = 0;
+  while (k < 40 && (1ull << k) < m) k++;
+  return k >= 1 && k <= NTT_MAX_K;
+}
+
+namespace {
+
+// LC j of constraint k on a row, normal form (r1cs_eval_row's sum)
+F4 lc_value(const R1csProgram& P, const uint8_t* row, uint32_t k, int j) {
+  F4 acc = {0, 0, 0, 0};
+  for (uint32_t q = P.lc_off[3ull * k + j]; q < P.lc_off[3ull * k + j + 1]; q++) {
+    const R1csTerm t = P.terms[q];
+    const F4 w = f_load(row + 32ull * t.wire);
+    if (t.coeff == 0) acc = f_add(acc, f_residue(w));
+    else if (t.coeff == 1) acc = f_sub(acc, f_residue(w));
+    else {
+      F4 cf;
+      memcpy(cf.data(), &P.coeffs[4ull * t.coeff], 32);
+      acc = f_add(acc, f_mul(cf, w));
+    }
+  }
+  return acc;
+}
+
+uint32_t bitrev(uint32_t i, int k) {
+  uint32_t r = 0;
+  for (int b = 0; b < k; b++) r |= ((i >> b) & 1u) << (k - 1 - b);
+  return r;
+}
+
+// evaluations on <w_N> -> evaluations on g <w_N>, in place, Montgomery form. W[j] = w_N^j, j < N / 2; g = w_2N;
+// n_inv = 1 / N. Decimation in frequency with the inverse roots (w^-e = -W[N / 2 - e]) leaves the coefficients
+// bit-reversed, the shift multiplies coefficient i at its place, decimation in time takes them back to natural order.
+void to_coset(std::vector<F4>& x, int k, const std::vector<F4>& W, const F4& g, const F4& n_inv) {
+  const size_t n = (size_t)1 << k;
+  const F4 zero = {0, 0, 0, 0};
+  for (int s = k - 1; s >= 0; s--) {
+    const size_t half = (size_t)1 << s;
+    for (size_t i = 0; i < n; i += 2 * half)
+      for (size_t jl = 0; jl < half; jl++) {
+        const size_t e = jl << (k - 1 - s);
+        const F4 u = x[i + jl], v = x[i + jl + half], d = f_sub(u, v);
+        x[i + jl] = f_add(u, v);
+        x[i + jl + half] = e ? f_mmul(d, f_sub(zero, W[n / 2 - e])) : d;
+      }
+  }
+  F4 gi = n_inv;
+  for (size_t i = 0; i < n; i++) {
+    F4& e = x[bitrev((uint32_t)i, k)];
+    e = f_mmul(e, gi);
+    gi = f_mmul(gi, g);
+  }
+  for (int s = 0; s < k; s++) {
+    const size_t half = (size_t)1 << s;
+    for (size_t i = 0; i < n; i += 2 * half)
+      for (size_t jl = 0; jl < half; jl++) {
+        const size_t e = jl << (k - 1 - s);
+        const F4 u = x[i + jl], v = e ? f_mmul(x[i + jl + half], W[e]) : x[i + jl + half];
+        x[i + jl] = f_add(u, v);
+        x[i + jl + half] = f_sub(u, v);
+      }
+  }
+}
+
+}  // namespace
+
+void r1cs_quotient_row(const R1csProgram& P, int k, const uint8_t* row, uint8_t* h) {
+  const size_t n = (size_t)1 << k;
+  const uint32_t nc = P.n_constraints, n_pub = P.n_pub_out + P.n_pub_in;
+  const F4 zero = {0, 0, 0, 0}, one = {1, 0, 0, 0};
+  std::vector<F4> a(n, zero), b(n, zero), c(n, zero);
+  for (uint32_t i = 0; i < nc; i++) {
+    a[i] = f_to_mont(lc_value(P, row, i, 0));
+    b[i] = f_to_mont(lc_value(P, row, i, 1));
+    c[i] = f_mmul(a[i], b[i]);
+  }
+  for (uint32_t s = 0; s <= n_pub; s++) a[nc + s] = f_to_mont(f_residue(f_load(row + 32ull * s)));
+  // g = w_2N = w_(2^28)^(2^(27 - k)), w_N = g^2, 1 / N = ((p + 1) / 2)^k
+  F4 g = f_to_mont(F_ROOT28);
+  for (int i = 0; i < 27 - k; i++) g = f_mmul(g, g);
+  const F4 w = f_mmul(g, g);
+  std::vector<F4> W(n / 2);
+  W[0] = f_to_mont(one);
+  for (size_t j = 1; j < n / 2; j++) W[j] = f_mmul(W[j - 1], w);
+  F4 half = FP;  // (p + 1) / 2 = (p >> 1) + 1, p odd
+  for (int i = 0; i < 4; i++) half[i] = (half[i] >> 1) | (i < 3 ? half[i + 1] << 63 : 0);
+  half[0] += 1;  // no carry: the low word of p >> 1 ends in ...000
+  const F4 half_m = f_to_mont(half);
+  F4 n_inv = f_to_mont(one);
+  for (int i = 0; i < k; i++) n_inv = f_mmul(n_inv, half_m);
+  to_coset(a, k, W, g, n_inv);
+  to_coset(b, k, W, g, n_inv);
+  to_coset(c, k, W, g, n_inv);
+  for (size_t j = 0; j < n; j++) f_store(h + 32 * j, f_mmul(f_sub(f_mmul(a[j], b[j]), c[j]), one));
+}
+
 }  // namespace pzk
 
 using namespace pzk;
@@ -339,6 +483,47 @@ static int r1cs_eval_host_impl(const pzk_r1cs* r, const uint8_t* h_wtns, size_t 
     if (n_failed) n_failed[i] = n;
   }
   return 0;
+}
+
+static int r1cs_quotient_info_impl(const pzk_r1cs* r, pzk_quotient_info* info) {
+  if (!r || !info) return api_fail(PZK_E_ARG, "null argument");
+  uint64_t m;
+  int k;
+  if (!r1cs_quotient_domain(r->prog, m, k))
+    return api_fail(PZK_E_ARG, "quotient: " + std::to_string(m) + " rows: the domain 2^k must have 1 <= k <= 24");
+  memset(info, 0, sizeof *info);
+  info->log2_n = (uint32_t)k;
+  info->tile = QUOT_TILE;
+  info->n = 1ull << k;
+  info->n_rows = m;
+  info->scratch_bytes = 2ull * QUOT_TILE * (32ull << k) + ntt_table_bytes(k);
+  return 0;
+}
+
+static int r1cs_quotient_host_impl(const pzk_r1cs* r, const uint8_t* h_wtns, size_t batch, size_t stride, uint8_t* h,
+                                   size_t h_stride) {
+  if (!r) return api_fail(PZK_E_ARG, "null argument");
+  if (batch == 0) return 0;
+  if (!h_wtns || !h) return api_fail(PZK_E_ARG, "null argument");
+  uint64_t m;
+  int k;
+  if (!r1cs_quotient_domain(r->prog, m, k))
+    return api_fail(PZK_E_ARG, "quotient: " + std::to_string(m) + " rows: the domain 2^k must have 1 <= k <= 24");
+  if ((uint64_t)r->prog.n_pub_out + r->prog.n_pub_in >= r->prog.n_wires)
+    return api_fail(PZK_E_ARG, "quotient: the header counts more public wires than wires");
+  if (stride < 32ull * r->prog.n_wires || stride % 16) return api_fail(PZK_E_ARG, "bad witness stride");
+  if (h_stride < (32ull << k) || h_stride % 16) return api_fail(PZK_E_ARG, "bad h stride");
+  for (size_t i = 0; i < batch; i++) r1cs_quotient_row(r->prog, k, h_wtns + stride * i, h + h_stride * i);
+  return 0;
+}
+
+int pzk_r1cs_quotient_info(const pzk_r1cs* r, pzk_quotient_info* info) {
+  return guarded([&] { return r1cs_quotient_info_impl(r, info); });
+}
+
+int pzk_r1cs_quotient_host(const pzk_r1cs* r, const uint8_t* h_wtns, size_t batch, size_t stride, uint8_t* h,
+                           size_t h_stride) {
+  return guarded([&] { return r1cs_quotient_host_impl(r, h_wtns, batch, stride, h, h_stride); });
 }
 
 int pzk_r1cs_load(const uint8_t* bytes, size_t len, pzk_r1cs** out) {

@@ -52,7 +52,19 @@ struct R1csDevice {
   R1csChunk* chunks = nullptr;
   uint32_t* long_list = nullptr;
   hipStream_t stream = nullptr;
+  // the quotient stage (kernels_quotient.hip), allocated at the first quotient call: the transforms' tables, and the
+  // b and c vectors of a tile of quot_rows witnesses
+  uint8_t* quot_tables = nullptr;
+  uint8_t* quot_scratch = nullptr;
+  uint32_t quot_rows = 0;
 };
+
+// The quotient's domain (pzkwit.h): M = n_constraints + n_pub_out + n_pub_in + 1 rows, N = 2^k >= M. false: k is
+// outside 1 .. 24.
+constexpr uint32_t QUOT_TILE = 8;  // witnesses per tile of scratch
+bool r1cs_quotient_domain(const R1csProgram& P, uint64_t& m, int& k);
+// one witness row -> h, 32 N bytes, normal form. Plain C++, no device (r1cs.cpp).
+void r1cs_quotient_row(const R1csProgram& P, int k, const uint8_t* row, uint8_t* h);
 
 }  // namespace pzk
 
@@ -64,9 +76,30 @@ struct pzk_r1cs {
   int device = -1;  // bound at the first check
   pzk::R1csDevice dev;
   void (*dev_free)(pzk_r1cs*) = nullptr;
+  double quot_ms[4] = {0, 0, 0, 0};  // pzk_r1cs_quotient_timing
 };
 
-#ifdef PZK_R1CS_KERNEL  // defined once, in kernels_r1cs.hip
+// the device half, shared by the check and the quotient (kernels_r1cs.hip): the device an object is bound to at its
+// first device call, and the upload of its program there (under the object's mutex, on the bound device)
+namespace pzk {
+struct R1csDevGuard {  // the caller's current device is restored on return (runtime.cpp DeviceGuard)
+  int prev = -1;
+  hipError_t err = hipSuccess;
+  explicit R1csDevGuard(int dev) {
+    err = hipGetDevice(&prev);
+    if (err == hipSuccess && prev != dev) err = hipSetDevice(dev);
+    else prev = -1;
+  }
+  ~R1csDevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+}  // namespace pzk
+struct pzk_exec;
+namespace pzk {
+int r1cs_bind(pzk_r1cs* r, const pzk_exec* ex);
+int r1cs_ensure_device(pzk_r1cs* r);
+}  // namespace pzk
+
+#ifdef PZK_R1CS_KERNEL  // defined in kernels_r1cs.hip and kernels_quotient.hip
 #include "fr.hpp"
 
 namespace pzk {
@@ -102,6 +135,7 @@ __device__ __forceinline__ void r1cs_report(int32_t* first_failed, uint32_t* n_f
   if (n_failed) atomicAdd(n_failed + witness, 1u);
 }
 
+#ifndef PZK_R1CS_NO_KERNELS  // kernels_quotient.hip takes the device functions only
 // The coefficient table, uploaded in normal form, to Montgomery form in place (once, at the first check).
 __global__ void __launch_bounds__(256) k_r1cs_coeffs(uint32_t* __restrict__ coeffs, uint32_t n) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -153,6 +187,8 @@ k_r1cs_check(const R1csChunk* __restrict__ chunks, uint32_t n_chunks, const uint
   }
 }
 
+#endif  // PZK_R1CS_NO_KERNELS
+
 // sum over the wave's 64 lanes, valid in lane 0; every lane of the wave calls it (outside any divergent branch: a
 // lane without a term passes 0)
 __device__ __forceinline__ fr r1cs_wave_sum(fr v) {
@@ -161,6 +197,7 @@ __device__ __forceinline__ fr r1cs_wave_sum(fr v) {
   return v;
 }
 
+#ifndef PZK_R1CS_NO_KERNELS
 // Long constraints: a wave per constraint (grid x over groups of four, strided) and witness tile (grid y, strided).
 // Lanes take the terms of each LC strided by 64 from global memory (contiguous 8-byte reads), the 64 partial sums
 // are reduced with fr_add over fr_shfl_down, lane 0 tests and reports. The loop bounds and the exit are uniform over
@@ -195,6 +232,8 @@ k_r1cs_check_long(const uint32_t* __restrict__ long_list, uint32_t n_long, const
     }
   }
 }
+
+#endif  // PZK_R1CS_NO_KERNELS
 
 }  // namespace pzk
 #endif

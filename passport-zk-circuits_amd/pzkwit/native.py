@@ -26,7 +26,8 @@ EXPORTS = ("pzk_instance_create", "pzk_instance_destroy", "pzk_instance_info", "
            "pzk_instance_input_packed", "pzk_pack_inputs", "pzk_unpack_inputs_host", "pzk_unpack_inputs",
            "pzk_witness_batch_packed", "pzk_witness_batch_host_packed", "pzk_passport_inputs_packed",
            "pzk_r1cs_load", "pzk_r1cs_destroy", "pzk_r1cs_get_info", "pzk_r1cs_check_batch",
-           "pzk_r1cs_check_batch_host", "pzk_r1cs_eval_host")
+           "pzk_r1cs_check_batch_host", "pzk_r1cs_eval_host", "pzk_r1cs_quotient_info", "pzk_r1cs_quotient_batch",
+           "pzk_r1cs_quotient_batch_host", "pzk_r1cs_quotient_host", "pzk_r1cs_quotient_timing")
 
 STATUS_NAMES = {
     0: "OK", 1: "Num2Bits (bitify.circom:26)", 2: "AliasCheck (aliascheck.circom:14)",
@@ -59,6 +60,11 @@ class PzkR1csInfo(ctypes.Structure):
                 ("n_prv_in", ctypes.c_uint32), ("n_labels", ctypes.c_uint64), ("n_constraints", ctypes.c_uint32),
                 ("n_long", ctypes.c_uint32), ("n_terms", ctypes.c_uint64), ("n_coeffs", ctypes.c_uint32),
                 ("max_terms", ctypes.c_uint32)]
+
+
+class PzkQuotientInfo(ctypes.Structure):
+    _fields_ = [("log2_n", ctypes.c_uint32), ("tile", ctypes.c_uint32), ("n", ctypes.c_uint64),
+                ("n_rows", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64)]
 
 
 class PzkExec(ctypes.Structure):
@@ -140,6 +146,13 @@ def lib():
         L.pzk_r1cs_check_batch_host.argtypes = L.pzk_r1cs_check_batch.argtypes
         L.pzk_r1cs_eval_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
                                          ctypes.c_void_p, ctypes.c_void_p]
+        L.pzk_r1cs_quotient_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(PzkQuotientInfo)]
+        L.pzk_r1cs_quotient_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(PzkExec)]
+        L.pzk_r1cs_quotient_batch_host.argtypes = L.pzk_r1cs_quotient_batch.argtypes
+        L.pzk_r1cs_quotient_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                             ctypes.c_void_p, ctypes.c_size_t]
+        L.pzk_r1cs_quotient_timing.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int]
         L.pzk_last_error.restype = ctypes.c_char_p
         L.pzk_version.restype = ctypes.c_char_p
         _lib = L

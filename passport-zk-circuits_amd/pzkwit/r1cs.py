@@ -5,6 +5,9 @@ circom_tester's circuit.checkConstraints(w), for whole batches, on the rows wher
     first_failed, n_failed = r.check(witness)        # (batch, n_wires, 32) uint8, through the device
     r.check_device(d_wtns, batch, stride, d_first)   # rows already in HBM (pzk_witness_batch's output)
 
+    h = r.quotient(witness)                          # Groth16's quotient evaluations, (batch, N, 32) uint8
+    r.quotient_device(d_wtns, batch, stride, d_h, h_stride)   # the same where the rows lie
+
 first_failed[i] is -1 when row i satisfies every constraint, else the lowest violated constraint index in file order.
 eval_host is the kernels' host twin (one thread, no device); check and check_device never fall back to it."""
 import ctypes
@@ -81,3 +84,41 @@ class R1cs:
         native._check(native.lib().pzk_r1cs_eval_host(self._h, a.ctypes.data, b, stride, first.ctypes.data,
                                                       n.ctypes.data))
         return first, n
+
+    # ---- Groth16's quotient evaluations (pzk_r1cs_quotient_*)
+    def quotient_info(self):
+        """{log2_n, tile, n, n_rows, scratch_bytes} of the quotient's domain (host only)"""
+        info = native.PzkQuotientInfo()
+        native._check(native.lib().pzk_r1cs_quotient_info(self._h, ctypes.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in native.PzkQuotientInfo._fields_}
+
+    def quotient_device(self, d_wtns, batch, stride, d_h, h_stride, stream=None, sync=True, device=-1, timing=False):
+        """pzk_r1cs_quotient_batch on device pointers (integers): rows batch x stride bytes in, batch x h_stride bytes
+        (>= 32 N) out. stream as for check_device."""
+        ex = native.PzkExec(device=device, flags=(native.PZK_EXEC_SYNC if sync else 0) | (2 if timing else 0), stream=stream)
+        native._check(native.lib().pzk_r1cs_quotient_batch(self._h, ctypes.c_void_p(d_wtns), batch, stride,
+                                                           ctypes.c_void_p(d_h), h_stride, ctypes.byref(ex)))
+
+    def quotient_timing(self, reset=False):
+        """ms of the stages of calls made with timing=True: [rows a b c, inverse x 3, forward a b, forward c + pointwise]"""
+        ms = (ctypes.c_double * 4)()
+        native._check(native.lib().pzk_r1cs_quotient_timing(self._h, ms, 1 if reset else 0))
+        return list(ms)
+
+    def quotient(self, witness):
+        """(batch, W >= n_wires, 32) uint8 -> h (batch, N, 32) uint8, on the GPU."""
+        a, b, stride = self._rows(witness)
+        n = self.quotient_info()["n"]
+        h = np.zeros((b, n, 32), dtype=np.uint8)
+        ex = native.PzkExec(device=-1, flags=0, stream=None)
+        native._check(native.lib().pzk_r1cs_quotient_batch_host(self._h, a.ctypes.data, b, stride, h.ctypes.data, 32 * n,
+                                                                ctypes.byref(ex)))
+        return h
+
+    def quotient_host(self, witness):
+        """The same through pzk_r1cs_quotient_host (plain C++, no device)."""
+        a, b, stride = self._rows(witness)
+        n = self.quotient_info()["n"]
+        h = np.zeros((b, n, 32), dtype=np.uint8)
+        native._check(native.lib().pzk_r1cs_quotient_host(self._h, a.ctypes.data, b, stride, h.ctypes.data, 32 * n))
+        return h
