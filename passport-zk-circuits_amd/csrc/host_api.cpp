@@ -12,11 +12,7 @@
 
 namespace pzk {
 
-int nsets_env(bool query) {
-  const char* e = getenv("PZK_NSETS");
-  const int v = e ? atoi(e) : query ? 6 : 3;
-  return v < 2 ? 2 : v > PIPELINE_SETS_MAX ? PIPELINE_SETS_MAX : v;
-}
+int pipeline_sets(bool query) { return query ? PIPELINE_SETS_MAX : 3; }
 
 // circom .sym text ("signal_idx,witness_idx,component_idx,name" per line; witness_idx -1 = eliminated)
 // -> inv[k] = O0 index of output witness element k (inv[0] = 0, the constant 1). Signal indices are the
@@ -229,7 +225,7 @@ static int layout_query_impl(const pzk_params* params, pzk_info* info, uint32_t*
   info->n_outputs = L.n_outputs;
   info->n_public_inputs = L.n_public;
   info->n_input_groups = (uint32_t)L.inputs.size();
-  info->pipeline_depth = nsets_env(params->circuit == PZK_CIRCUIT_QUERY);
+  info->pipeline_depth = pipeline_sets(params->circuit == PZK_CIRCUIT_QUERY);
   if (n_regions) *n_regions = (uint32_t)L.regions.size();
   return 0;
 }

@@ -1,5 +1,5 @@
-"""GPU: the scheduling paths of calls left in flight (runtime.cpp batch_locked / ensure_chain_streams), each
-against the CPU oracle rather than against another run of the same code:
+"""GPU: the scheduling paths of calls left in flight (runtime.cpp: batch_locked, the circuits' schedule_* functions
+and ensure_chain_streams), each against the CPU oracle rather than against another run of the same code:
 
 * two register instances on one device, so both take the reduced stream set (low-priority SMT chain streams, no
   post-chain stream); calls alternate between them without synchronising, then one instance is destroyed and the
@@ -9,7 +9,9 @@ against the CPU oracle rather than against another run of the same code:
 * QueryIdentity(80) with more calls in flight than it has scratch sets' worth of chain streams (six sets over four
   chain streams): eight unsynchronised calls;
 * the same with 13 rows per call (query: eight calls; register: two), so the workgroups of the kernels that share one
-  inversion among their witnesses (k_qry_prep, k_rsa_inv, k_bjj_core) are partly live while other calls are in flight.
+  inversion among their witnesses (k_qry_prep, k_rsa_inv, k_bjj_core) are partly live while other calls are in flight;
+* an ECDSA (SIGNATURE_TYPE 20) and an RSA-PSS (SIGNATURE_TYPE 10) instance with three unsynchronised calls of 4 rows:
+  the signature chain's waits for the SHA core and the EC tables, and the PSS chain between two SHA core launches.
 
 Rows of every call are compared element for element with the oracle (sampled rows of each call)."""
 import numpy as np
@@ -21,13 +23,13 @@ from pzkwit.field import SplitMix64
 pytestmark = pytest.mark.gpu
 
 
-def _register_rows(seed, n, depth):
-    g = I.PassportGen(seed=seed, n_keys=2, params=I.CANONICAL, workers=1)
-    return np.stack([I.pack_register_inputs(g.passport_at(i, smt_depth=depth(i)), I.CANONICAL) for i in range(n)])
+def _register_rows(seed, n, depth, params=I.CANONICAL):
+    g = I.PassportGen(seed=seed, n_keys=2, params=params, workers=1)
+    return np.stack([I.pack_register_inputs(g.passport_at(i, smt_depth=depth(i)), params) for i in range(n)])
 
 
-def _check_rows(oracle, rows, out, st, picks, inv=None):
-    prm = oracle.register_params(**I.CANONICAL)
+def _check_rows(oracle, rows, out, st, picks, inv=None, params=I.CANONICAL):
+    prm = oracle.register_params(**params)
     for r in picks:
         rc, ref = oracle.register_witness(prm, rows[r])
         assert rc == 0 and st[r] == 0, (r, rc, st[r])
@@ -137,5 +139,20 @@ def test_register_odd_batches_in_flight(oracle):
     for _, lo, out, st in res:
         assert (st == 0).all()
         _check_rows(oracle, rows[lo:lo + ODD], out, st, [7, 8, 12])
+    del d_in
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("sig", [20, 10])
+def test_ecdsa_and_pss_calls_in_flight(oracle, sig):
+    """the first two calls' SMT chains run on different chain streams, the third re-enters the rotation while the
+    first may still be emitting; 4 rows leave every shared-inversion workgroup partly live"""
+    import torch
+    params = I.instance_params(sig)
+    inst = native.Instance(native.PZK_CIRCUIT_REGISTER, 0, params)
+    rows = _register_rows(0x73, 12, lambda i: (7 * i) % 80, params)  # (a seed whose two e = 3 keys come quickly)
+    res, d_in = _calls(torch, [inst], rows, 3, 4)
+    for _, lo, out, st in res:
+        _check_rows(oracle, rows[lo:lo + 4], out, st, [0, 3], params=params)
     del d_in
     torch.cuda.empty_cache()
