@@ -102,6 +102,29 @@ def test_register_smt_depth_matches_oracle(oracle, gen):
     _check(oracle, I.CANONICAL, np.stack(rows))
 
 
+def test_register_smt_interior_zero_siblings_match_oracle(oracle, gen):
+    """slaveMerkleInclusionBranches with empty siblings inside the path (valid proofs that the generator never draws:
+    its siblings below the depth are all non-zero), through k_smt_prep's isZero mask and the chain: an empty sibling at
+    level 0 and at the first level of the second lane segment, level 78 alone, every other level, between two plain
+    proofs. The branches and the root (key = value = the public key's hash) are written into the packed rows."""
+    from pzkwit import query as Q
+    from query_cases import NL
+    masks = [(40, ()), (40, (0, NL)), (79, range(78)), (79, range(0, 79, 2)), (79, ())]
+    rows = []
+    for i, (depth, zeros) in enumerate(masks):
+        pp = gen.passport_at(120 + i, smt_depth=depth)
+        row = I.pack_register_inputs(pp)
+        sib = list(pp["siblings"])
+        for z in zeros:
+            assert sib[z]
+            sib[z] = 0
+        first = row.shape[0] - 81  # the 80 branches, then skIdentity
+        for k, v in enumerate([Q.smt_root(pp["pk_hash"], pp["pk_hash"], sib)] + sib):
+            row[first + k - 1 if k else 0] = np.frombuffer(v.to_bytes(32, "little"), dtype=np.uint8)
+        rows.append(row)
+    _check(oracle, I.CANONICAL, np.stack(rows))
+
+
 PARAM_VARIANTS = [
     dict(I.CANONICAL, doc=1),                      # TD1 chunking (190-bit dg1 chunks)
     dict(I.CANONICAL, aa=0),                       # no active authentication
