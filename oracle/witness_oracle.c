@@ -1852,10 +1852,27 @@ static void orc_init(void) {
  * HASH_BLOCK_SIZE (registerIdentityBuilder.circom:151), so the block sizes agree or there is no dg15 */
 static int params_ok(const orc_params *P) {
   const int HT = sig_hash(P->sig);
-  return ((P->sig >= 1 && P->sig <= 4) || is_pss(P->sig) || (ec_index(P->sig) >= 0 && EC_GPOW_T[ec_index(P->sig)])) &&
-         (P->dg_hash == 256 || P->dg_hash == 224 || P->dg_hash == 160 || P->dg_hash == 384) && P->dg_hash <= ec_hash(P->sig) &&
-         (hblock(P->dg_hash) == hblock(HT) || P->dg15_blocks == 0) && (P->doc == 1 || P->doc == 3) && (P->aa >= 0 && P->aa <= 25) &&
-         P->ec_blocks > 0 && P->ec_blocks <= 16 && P->dg15_blocks >= 0 && P->dg15_blocks <= 16;
+  if (!(((P->sig >= 1 && P->sig <= 4) || is_pss(P->sig) || (ec_index(P->sig) >= 0 && EC_GPOW_T[ec_index(P->sig)])) &&
+        (P->dg_hash == 256 || P->dg_hash == 224 || P->dg_hash == 160 || P->dg_hash == 384) && P->dg_hash <= ec_hash(P->sig) &&
+        (hblock(P->dg_hash) == hblock(HT) || P->dg15_blocks == 0) && (P->doc == 1 || P->doc == 3) && (P->aa >= 0 && P->aa <= 25) &&
+        P->ec_blocks > 0 && P->ec_blocks <= 16 && P->dg15_blocks >= 0 && P->dg15_blocks <= 16))
+    return 0;
+  /* every index the templates read lies inside its signal array, or circom does not compile the instance: the flow's
+   * encapsulatedContent[DG1_SHIFT + i], [DG15_SHIFT + i], [DG15_SHIFT - 24 + i] and signedAttributes[EC_SHIFT + i]
+   * (passportVerificationFlow.circom:31,46,59,74), RegisterIdentity's dg15[AA_SHIFT + ...] over 1024 bits of an RSA key or
+   * 2 x EC_FIELD_SIZE of an EC key (identity.circom:25-84), which also needs a dg15 to read. Without active
+   * authentication the flow gets DG15_ACTUAL_SHIFT = DG_HASH_TYPE and DG15_SHIFT / AA_SHIFT are unused. 64-bit sums:
+   * the shifts are the caller's 32-bit integers. */
+  const int64_t DG = P->dg_hash, ecLen = (int64_t)P->ec_blocks * hblock(HT), d15Len = (int64_t)P->dg15_blocks * hblock(HT);
+  const int64_t dg15shift = P->aa ? P->dg15_shift : DG;
+  if (P->dg1_shift < 0 || (int64_t)P->dg1_shift + DG > ecLen || dg15shift < 24 || dg15shift + DG > ecLen) return 0;
+  /* the flow compares DG bits at EC_SHIFT, and DG > HASH_TYPE for SIG 24 (HASH_TYPE 224, EC_HASH_TYPE 256) with DG 256 */
+  if (P->ec_shift < 0 || (int64_t)P->ec_shift + (HT > DG ? HT : DG) > 1024) return 0;
+  if (P->aa) {
+    const int64_t span = aa_is_ec(P->aa) ? 2 * (int64_t)aa_field(P->aa) : 1024;
+    if (P->dg15_blocks < 1 || P->aa_shift < 0 || (int64_t)P->aa_shift + span > d15Len) return 0;
+  }
+  return 1;
 }
 
 size_t orc_register_n_inputs(const orc_params *P) {

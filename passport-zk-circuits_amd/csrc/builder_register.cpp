@@ -95,10 +95,11 @@ bool build_register(const pzk_params& p, Layout& L, std::string& why) {
           "RegisterIdentity's dg15[DG15_SIZE * DG_HASH_BLOCK_SIZE] (identity.circom:22)";
     return false;
   }
-  // (64-bit sums: the shifts are caller-supplied int32)
+  // (64-bit sums: the shifts are caller-supplied int32). The flow reads signedAttributes[EC_SHIFT + i] for i < DG
+  // (passportVerificationFlow.circom:55-59), and DG > HT is possible: SIG 24 (HT 224, EHT 256) with DG 256
   const int64_t dg15shift = aa ? p.dg15_shift : DG;
   if (p.dg1_shift < 0 || (int64_t)p.dg1_shift + DG > ecLen || dg15shift < 24 || dg15shift + DG > ecLen ||
-      p.ec_shift < 0 || (int64_t)p.ec_shift + HT > 1024 ||
+      p.ec_shift < 0 || (int64_t)p.ec_shift + (HT > DG ? HT : DG) > 1024 ||
       (aa && (p.aa_shift < 0 || (int64_t)p.aa_shift + (aa_ec ? 2 * aa_f : 1024) > d15Len))) {
     why = "shift parameters address bits outside the inputs";
     return false;
